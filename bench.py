@@ -1,8 +1,13 @@
 #!/usr/bin/env python3
 """Throughput benchmark of the MI355X DistilCodec encode -> VQ -> decode path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4]
-    python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c4] [--dump-outputs DIR] [--full]
+    python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N [--full]
+
+A plain run does only what the headline figure needs: it builds the engine and the resident batch,
+runs W untimed and K timed steps, writes the last step's outputs when --dump-outputs is given, and
+prints the result line (`value`, `ms_per_step`; the sub-records below are null).  Everything else
+the benchmark measures or checks runs only with --full.
 
 Workloads (BASELINE.json configs):
   c2 (default; configs[1]): 32 synthetic 10 s 24 kHz clips PER GPU (speech-like / music-like),
@@ -13,8 +18,8 @@ Workloads (BASELINE.json configs):
 Both run through the shipped multi-GPU path (`sharding.ShardedEncodeDecode`): rank r holds its
 contiguous shard of the global clip list, resident in HBM; a step = `dcx_encode_decode` over the
 shard plus the all_gather of every rank's codes (RCCL over xGMI).  Clips are independent, so there
-is no collective on the data path (weak scaling); the gather is the only exchange.  With the
-default c2 workload the same line carries sub-records (each skippable by a flag):
+is no collective on the data path (weak scaling); the gather is the only exchange.  With --full and
+the default c2 workload the same line carries sub-records (each skippable by a flag):
   "c4"             a C4 pass (128 ragged clips per GPU, padded to the global max), at every N;
   "c3"             (N = 1) configs[2]: encoder + GRFVQ token extraction, 256 x 10 s, bf16;
   "c5"             (N = 1) configs[4]: 1 s hops through one captured hipGraph (split-K latency mode);
@@ -23,8 +28,12 @@ default c2 workload the same line carries sub-records (each skippable by a flag)
                    bit-exact vs CPU" clause, measured on the benchmarked workload).
 
 Rank 0 prints one JSON line.  `value` counts real (unpadded) clip samples of all ranks per second.
-`roofline` reports the dominant kernel (largest summed device time, HIP events around each launch
-on its stream during the timed steps) as algorithmic FLOP/s against its MFMA ceiling;
+--dump-outputs DIR writes what the last timed step returned to its caller, DIR/codes.npy (the
+gathered codes) and DIR/wav.npy (this rank's waveforms), as float32, at most 64 MB in all (a fixed,
+seeded sample of the rows of a larger array).  Clips and weights are seeded, so two builds run with
+the same arguments can be compared output for output.
+With --full, `roofline` reports the dominant kernel (largest summed device time, HIP events around
+each launch on its stream during the timed steps) as algorithmic FLOP/s against its MFMA ceiling;
 `cpu_baseline` times the CPU oracle (the reference's algorithm on PyTorch-CPU,
 oracle/reference_cpu.py) on a bounded sample on this host, all cores and 1 thread, median of 3.
 """
@@ -254,6 +263,33 @@ def codes_vs_oracle(eng, runner, cfg, state):
             "waveform_of": of, "oracle_seconds": round(t_ref, 2)}
 
 
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path: str, arrays: dict, budget: int = DUMP_BUDGET_BYTES, seed: int = 0) -> dict:
+    """Write each array as `path`/<name>.npy in float32 (float64 stays float64), `budget` bytes at
+    most in all.  An array over its share of the budget (split in proportion to the sizes) is cut
+    to a sample of its rows: sorted indices drawn without replacement from PCG64(seed), the same
+    for every run of the same shapes.  Returns name -> the saved shape."""
+    os.makedirs(path, exist_ok=True)
+    out = {n: np.asarray(a) for n, a in arrays.items()}
+    out = {n: a if a.dtype == np.float64 else a.astype(np.float32) for n, a in out.items()}
+    total = sum(a.nbytes for a in out.values())
+    shapes = {}
+    for i, (name, a) in enumerate(out.items()):
+        share = budget if total <= budget else budget * a.nbytes // total
+        if a.nbytes > share:
+            row_bytes = max(1, a.nbytes // a.shape[0])
+            keep = share // row_bytes
+            if keep < 1:
+                raise ValueError(f"one row of {name} ({row_bytes} bytes) is over its share of the {budget}-byte budget")
+            rows = np.sort(np.random.Generator(np.random.PCG64(seed + i)).choice(a.shape[0], size=keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(path, f"{name}.npy"), np.ascontiguousarray(a))
+        shapes[name] = tuple(a.shape)
+    return shapes
+
+
 def make_runner(eng, workload: str, rank: int, world: int, seed: int = 0):
     per_gpu, longest, shortest = WORKLOADS[workload]
     n_total = per_gpu * world
@@ -265,7 +301,8 @@ def make_runner(eng, workload: str, rank: int, world: int, seed: int = 0):
 
 
 def run_timed(runner, steps: int, warmup: int, world: int, dev, profile_eng=None):
-    """W untimed steps, then K steps between barrier + synchronize; max over ranks."""
+    """W untimed steps, then K steps between barrier + synchronize; max over ranks.  Returns the
+    seconds, the per-kernel profile and what the last timed step returned (all codes, local wav)."""
     for _ in range(warmup):
         runner.step()
     torch.cuda.synchronize(dev)
@@ -281,7 +318,7 @@ def run_timed(runner, steps: int, warmup: int, world: int, dev, profile_eng=None
     torch.cuda.synchronize(dev)
     t0 = time.perf_counter()
     for _ in range(steps):
-        all_codes, _ = runner.step()
+        all_codes, wav = runner.step()
     torch.cuda.synchronize(dev)
     if world > 1:
         dist.barrier()
@@ -295,7 +332,7 @@ def run_timed(runner, steps: int, warmup: int, world: int, dev, profile_eng=None
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
         assert all_codes.shape[0] == runner.n_total
-    return dt, prof
+    return dt, prof, (all_codes, wav)
 
 
 def roofline(prof: dict, steps: int):
@@ -317,12 +354,18 @@ def roofline(prof: dict, steps: int):
             "share_of_device_time": round(rec["ms"] / sum(r["ms"] for r in prof.values()), 4)}
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", choices=sorted(WORKLOADS), default="c2")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's codes and waveforms to DIR/<name>.npy (float32, <= 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the per-launch roofline timing, the "
+                         "codes_vs_oracle check, the C4 / C5 / f32_ieee / C3 sub-records and the CPU baseline "
+                         "(each skippable by its --no-* flag, which has no effect without --full)")
     ap.add_argument("--no-c4", action="store_true", help="skip the extra C4 pass")
     ap.add_argument("--no-c3", action="store_true", help="skip the C3 token-extraction sub-record (N = 1)")
     ap.add_argument("--no-c5", action="store_true", help="skip the C5 streaming-hop sub-record (N = 1)")
@@ -334,7 +377,17 @@ def main():
                     help="x6 (DCX_GEMM_X6): fp32-tolerance emulation, h3 (2 fp16 values, 3 products) for the wide "
                          "generator convs and the ConvNeXt 1x1 convs, x6 (3 bf16 planes, 6 products) elsewhere, fp32 "
                          "accumulation; f32: IEEE fp32 MFMA")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
+
+
+def main():
+    args = parse_args()
+    full = args.full
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -358,7 +411,10 @@ def main():
     eng = NativeCodec(cfg, state, dev, gemm=args.gemm)
 
     runner, samples, n_total = make_runner(eng, args.config, rank, world)
-    dt, prof = run_timed(runner, args.steps, args.warmup, world, dev, None if args.no_profile else eng)
+    dt, prof, last = run_timed(runner, args.steps, args.warmup, world, dev, eng if full and not args.no_profile else None)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"codes": last[0].cpu().numpy(), "wav": last[1].cpu().numpy()})
+    del last
     ms_step = dt / args.steps * 1e3
     value = samples / (dt / args.steps)
     padded = n_total * (runner.audio.shape[1] - 1)
@@ -369,14 +425,14 @@ def main():
             json.dump({"steps": args.steps, "kernels": prof}, f, indent=1)
 
     oracle_codes = None
-    if world == 1 and args.config == "c2" and not args.no_oracle_codes:
+    if full and world == 1 and args.config == "c2" and not args.no_oracle_codes:
         oracle_codes = codes_vs_oracle(eng, runner, cfg, state)
 
     c4 = None
-    if args.config == "c2" and not args.no_c4:
+    if full and args.config == "c2" and not args.no_c4:
         r4, s4, n4 = make_runner(eng, "c4", rank, world)
         k4 = min(args.steps, 3 if world > 1 else 2)
-        dt4, _ = run_timed(r4, k4, 1, world, dev)
+        dt4, _, _ = run_timed(r4, k4, 1, world, dev)
         c4 = {"workload": f"C4: {n4} ragged clips (9-10 s, speech+music), {n4 // world} per GPU, padded to the global max",
               "value": round(s4 / (dt4 / k4), 1), "unit": "samples/s (real, unpadded)",
               "ms_per_step": round(dt4 / k4 * 1e3, 3), "steps": k4, "warmup": 1, "global_batch": n4,
@@ -385,28 +441,28 @@ def main():
         torch.cuda.empty_cache()
 
     c5 = None
-    if world == 1 and args.config == "c2" and args.gemm == "x6" and not args.no_c5:
+    if full and world == 1 and args.config == "c2" and args.gemm == "x6" and not args.no_c5:
         c5 = c5_record(eng)
 
     f32 = None
-    if world == 1 and args.gemm == "x6" and not args.no_f32:
+    if full and world == 1 and args.gemm == "x6" and not args.no_f32:
         eng.set_gemm("f32")
         kf = min(args.steps, 2)
-        dtf, _ = run_timed(runner, kf, 1, world, dev)
+        dtf, _, _ = run_timed(runner, kf, 1, world, dev)
         eng.set_gemm("x6")
         f32 = {"value": round(samples / (dtf / kf), 1), "unit": "samples/s", "ms_per_step": round(dtf / kf * 1e3, 3),
                "steps": kf, "arith": "IEEE fp32 MFMA (v_mfma_f32_32x32x2_f32), same workload",
                "tflops": round(samples / 256 * MFLOP_PER_FRAME * 1e6 / (dtf / kf) / 1e12, 1)}
 
     c3 = None
-    if world == 1 and args.config == "c2" and not args.no_c3:
+    if full and world == 1 and args.config == "c2" and not args.no_c3:
         del runner
         eng._ws = None  # the C2 / C4 workspace is not needed by the token-extraction handle
         torch.cuda.empty_cache()
         c3 = c3_record(cfg, state, dev)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(cfg, state)
 
     if rank == 0:

@@ -1,6 +1,6 @@
 """bench.py's N > 1 path end to end on the one-GPU box: two ranks under torch.distributed.run, the
 shipped ShardedEncodeDecode per rank, barriers and max-over-ranks timing, the codes all_gather inside
-the timed step and the C4 pass at N = 2 (global batch 256).  Both ranks share cuda:0 and gloo carries
+the timed step and (--full) the C4 pass at N = 2 (global batch 256).  Both ranks share cuda:0 and gloo carries
 the collectives (DCX_BENCH_ONE_DEVICE=1): RCCL refuses two ranks on one device, so the "nccl"
 branch itself runs only on the driver's multi-GPU node."""
 import json
@@ -27,7 +27,7 @@ def test_bench_two_ranks_one_device():
     env = dict(os.environ, DCX_BENCH_ONE_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1",
-           "--warmup", "1"]
+           "--warmup", "1", "--full"]
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

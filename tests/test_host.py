@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
 
 def test_token_table_matches_reference_fixture(golden, cfg):
     from distilcodec_nabeel_amd import tokens
@@ -51,9 +53,8 @@ def test_config_checks(cfg):
     from distilcodec_nabeel_amd import config
 
     config.check_supported(cfg)
-    ref = "/root/reference/configs/model_config.json"
-    if os.path.exists(ref):
-        config.check_supported(config.load_config(ref))
+    # the reference's configs/model_config.json, stored as a fixture
+    config.check_supported(config.load_config(os.path.join(GOLDEN, "model_config.json")))
     bad = copy.deepcopy(cfg)
     bad["quantizer"]["n_groups"] = 2
     with pytest.raises(ValueError):
@@ -100,9 +101,7 @@ def test_wav_roundtrip(tmp_path):
 def test_reference_wav_is_readable():
     from distilcodec_nabeel_amd import audio_io
 
-    p = "/root/reference/data/org_audios/0000.wav"
-    if not os.path.exists(p):
-        pytest.skip("reference data only exists in the build container")
+    p = os.path.join(GOLDEN, "ref_0000.wav")  # the reference's data/org_audios/0000.wav, stored as a fixture
     y, sr = audio_io.load_wav(p, 24000)
     assert sr == 24000 and y.ndim == 1 and y.shape[0] == 280968 and np.abs(y).max() <= 1.0
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Per-kernel table from bench.py's DCX_BENCH_KERNELS json."""
+"""Per-kernel table from the DCX_BENCH_KERNELS json that `bench.py --full` writes."""
 import json
 import sys
 
