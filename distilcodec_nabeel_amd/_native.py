@@ -82,6 +82,11 @@ SIGNATURES = {
     "dcx_vq_decode": (ctypes.c_int, [_P, _P, _I32, _I64, _P, _P, _P, _SZ, _P]),
     "dcx_generate": (ctypes.c_int, [_P, _P, _I32, _I64, _P, _P, _SZ, _P]),
     "dcx_encode_decode": (ctypes.c_int, [_P, _P, _I32, _I64, _P, _P, _P, _SZ, _P]),
+    "dcx_ragged_plan_size": (_I64, [_I32]),
+    "dcx_ragged_plan": (ctypes.c_int, [_P, ctypes.POINTER(_I64), _I32, _P, _I64, ctypes.POINTER(_I64),
+                                       ctypes.POINTER(_I64)]),
+    "dcx_ragged_workspace_size": (_SZ, [_P, _I32, _I64]),
+    "dcx_tokenize_ragged": (ctypes.c_int, [_P, _P, _P, _P, _I32, _I64, _I64, _P, _P, _P, _P, _SZ, _P]),
     "dcx_transpose": (ctypes.c_int, [_P, _P, _I32, _I64, _I64, _P]),
     "dcx_mp3_info": (ctypes.c_int, [_P, _SZ, ctypes.POINTER(_I64), ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
     "dcx_mp3_decode": (ctypes.c_int, [_P, _SZ, _P, _I64]),

@@ -261,6 +261,10 @@ class DistilCodec:
 
     def preprocess_raw_audio_batch(self, audio_data_info_list: list):
         """distil_codec.py:99-145: items are [audio (samples,) or (channels, samples), sr]."""
+        return self._finish_preprocess(self._raw_audio_list(audio_data_info_list))
+
+    def _raw_audio_list(self, audio_data_info_list: list) -> list:
+        """The per-clip half of distil_codec.py:99-131: mono float32 at the model rate."""
         audio_list = []
         sr_target = self.spec_config.sampling_rate
         for audio, sampling_rate in audio_data_info_list:
@@ -270,7 +274,7 @@ class DistilCodec:
             if a.ndim == 2:
                 a = a.mean(axis=0) if a.shape[0] > 1 else a[0]
             audio_list.append(a)
-        return self._finish_preprocess(audio_list)
+        return audio_list
 
     def _read_audio_files(self, audio_pathes: list) -> list:
         """The file-reading half of distil_codec.py:147-198: mono float32 per path at the model rate.
@@ -314,9 +318,14 @@ class DistilCodec:
         return tokens.audio_tokenize(self.gr_audio_code2token, codes, n_groups, n_residual)
 
     # ---------------------------------------------------------------- encode / decode
-    def encode(self, audio_pathes: list, enable_bfloat16: bool = False, raw_audio: bool = False, codes_only: bool = False):
+    def encode(self, audio_pathes: list, enable_bfloat16: bool = False, raw_audio: bool = False, codes_only: bool = False,
+               ragged: bool = False):
         """distil_codec.py:545-573 -> (GRVQResult, gen_time_lengths, n_hop_lengths).
-        `codes_only=True` (opt-in, not in the reference) skips quantized / feature outputs."""
+        `codes_only=True` (opt-in, not in the reference) skips quantized / feature outputs.
+        `ragged=True` (opt-in, not in the reference): the clips are tokenized packed, without padding,
+        so every clip's codes are those it gives alone, whatever shares its batch (`_encode_ragged`)."""
+        if ragged:
+            return self._encode_ragged(audio_pathes, enable_bfloat16, raw_audio, codes_only)
         if raw_audio:
             _, mel_specs, gen_time_lengths, n_hop_lengths = self.preprocess_raw_audio_batch(audio_pathes)
         else:
@@ -339,6 +348,35 @@ class DistilCodec:
             if want:
                 ret.x_pjt_in_list.append(pin[b, :hop_len].reshape(hop_len * 2, -1).cpu())
                 ret.quantized_fup_list.append(fup[b, :hop_len].reshape(hop_len * 2, -1).cpu())
+        return ret, gen_time_lengths, n_hop_lengths
+
+    def _encode_ragged(self, audio_pathes: list, enable_bfloat16: bool, raw_audio: bool, codes_only: bool):
+        """`encode(..., ragged=True)`: `codes` is (1, B, T_max, 1) int64 with -1 (the reference's masked
+        code, which `quantizer.decode` accepts) beyond each clip's own frames; `codes_list` and the
+        `_list` features are trimmed per clip as in `encode`; `x_pjt_in` / `quantized_fup` are the
+        packed (sum T, codebook_dim) tensors (None with `codes_only`); `quantized` is None."""
+        audio_list = self._raw_audio_list(audio_pathes) if raw_audio else self._read_audio_files(audio_pathes)
+        n_hop_lengths, gen_time_lengths = (list(v) for v in zip(*[self._lengths(a.shape[0]) for a in audio_list]))
+        want = not codes_only
+        with self._precision(enable_bfloat16) as eng:
+            codes, offsets, pin, fup = eng.tokenize_ragged(audio_list, want_pjt_in=want, want_fup=want)
+        off = offsets.tolist()
+        B = len(audio_list)
+        t_max = max(off[b + 1] - off[b] for b in range(B))
+        padded = torch.full((B, t_max), -1, dtype=torch.int64, device=codes.device)
+        for b in range(B):
+            padded[b, : off[b + 1] - off[b]] = codes[off[b]: off[b + 1]]
+        zero = torch.zeros((), device=codes.device)
+        ret = GRVQResult(quantized=None, codes=padded[None, :, :, None], codes_list=[], total_loss=zero,
+                         commitment_loss=zero.clone(), codebook_diversity_loss=zero.clone(), quantized_fup=fup,
+                         quantized_fup_list=[], x_pjt_in=pin, x_pjt_in_list=[])
+        codes_host = codes.cpu()
+        for b, hop_len in enumerate(n_hop_lengths):
+            codes_t = codes_host[off[b]: off[b] + hop_len].tolist()
+            ret.codes_list.append(self.audio_tokenize(codes=codes_t, n_groups=self.ngroups, n_residual=self.nresiduals))
+            if want:
+                ret.x_pjt_in_list.append(pin[off[b]: off[b] + hop_len].reshape(hop_len * 2, -1).cpu())
+                ret.quantized_fup_list.append(fup[off[b]: off[b] + hop_len].reshape(hop_len * 2, -1).cpu())
         return ret, gen_time_lengths, n_hop_lengths
 
     def _check_codes(self, codes: torch.Tensor) -> None:

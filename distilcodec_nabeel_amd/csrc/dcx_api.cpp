@@ -103,6 +103,9 @@ struct dcx_codec {
 
   ConvW dft, melfb;
   ConvW stem;
+  // one-tap views of the DFT and the stem for ragged batches (dcx_tokenize_ragged): the same packed
+  // weights read as [Cout][taps * Cin] (every packing is tap-major), over whole frames / unfolded rows
+  ConvW dft1, stem1;
   LnW stem_ln, enc_norm;
   LnW ds_ln[4];
   ConvW ds_conv[4];
@@ -695,6 +698,7 @@ struct ConvCall {
   int epi = dcx::EPI_BIAS, mean = dcx::MEAN_NONE;
   bool exact = false;  // keep x6 arithmetic in bf16 mode (the reference's fp32 mel front end)
   bool silu_in = false;  // fp32 input: the conv consumes silu(x) (applied while staging)
+  bool fixed_tiles = false;  // ConvParams::fixed_tiles: the kernel family does not follow the row count
   // h3 range (round 6): the bound program of an h2 output, where its per-clip shift goes, and where
   // the per-clip max |v| of the output goes (ConvParams::yb / y_ash / y_amax)
   dcx::RangeProg yb{};
@@ -802,6 +806,7 @@ int conv_params(dcx_codec* h, const ConvW& w, const ConvCall& c, bool force_f32,
   p.nprod = one ? 1 : 6;
   p.round_bf16 = one;
   p.silu_in = c.silu_in;
+  p.fixed_tiles = c.fixed_tiles ? 1 : 0;
   p.x_compact = x6 && c.x.p && c.x.c1 ? 1 : 0;
   p.y_compact = c.y6 ? c.y6c : 0;
   p.y6s_h2 = c.y6s && c.y6s_h2 ? 1 : 0;
@@ -1153,8 +1158,9 @@ int ensure_planes(dcx_codec* h, CAct& a, long long rows, int C, Bump& ws, hipStr
 // scratch, written compact where their consumer takes it (bf16 mode), or in h2 with per-row ranges
 // (ln.row_ash / row_amax, hid.row_ash: the LayerNorm's exact row maxima, the hidden's rows bounded
 // by g1 max|LN row| + max|b1|; round 6).
+// rg: the rows are a ragged batch (B = 1, T = its total frames): the depthwise conv stays inside each clip.
 int run_block(dcx_codec* h, const BlockW& bw, float* x, unsigned short* out6, int B, int T, Act ln, Act hid,
-              hipStream_t s, int out6c = 0) {
+              hipStream_t s, int out6c = 0, const dcx::RaggedSeg* rg = nullptr) {
   const long long M = (long long)B * T;
   const int C = bw.C;
   if (out6 && out6c == 3) return fail(h, DCX_ERR_STATE, "internal: a block output in h2 goes through launch_h2_rows");
@@ -1166,9 +1172,16 @@ int run_block(dcx_codec* h, const BlockW& bw, float* x, unsigned short* out6, in
   hid.r = Rng{};
   ln.r.ash_row = ln.row_ash;
   hid.r.ash_row = hid.row_ash;
-  LAUNCH(h, s, "dwconv_ln", 14.0 * M * C, 8.0 * M * C,
-         dcx::launch_dwconv_ln(x, ln.f, ln.p, ln.c1 ? 1 : ln.h2 ? 3 : 0, bw.dww, bw.dwb, bw.ln.w, bw.ln.b, B, T, C,
-                               h->gemm_mode == DCX_GEMM_BF16 ? 1 : 0, &h->knobs, s, ln.row_ash, ln.row_amax));
+  if (rg) {
+    if (B != 1 || T != rg->rows) return fail(h, DCX_ERR_STATE, "internal: ragged block rows");
+    LAUNCH(h, s, "dwconv_ln_ragged", 14.0 * M * C, 8.0 * M * C,
+           dcx::launch_dwconv_ln_ragged(x, ln.f, ln.p, ln.c1 ? 1 : ln.h2 ? 3 : 0, bw.dww, bw.dwb, bw.ln.w, bw.ln.b, *rg, C,
+                                        h->gemm_mode == DCX_GEMM_BF16 ? 1 : 0, &h->knobs, s, ln.row_ash, ln.row_amax));
+  } else {
+    LAUNCH(h, s, "dwconv_ln", 14.0 * M * C, 8.0 * M * C,
+           dcx::launch_dwconv_ln(x, ln.f, ln.p, ln.c1 ? 1 : ln.h2 ? 3 : 0, bw.dww, bw.dwb, bw.ln.w, bw.ln.b, B, T, C,
+                                 h->gemm_mode == DCX_GEMM_BF16 ? 1 : 0, &h->knobs, s, ln.row_ash, ln.row_amax));
+  }
   ConvCall c1 = pointwise(ln, M);
   c1.out_to(hid);
   c1.epi = dcx::EPI_GELU;
@@ -1209,6 +1222,19 @@ void row_ranges(dcx_codec* h, Bump& ws, long long M, Act& ln, Act& hid) {
 }
 
 // ---------------- stage bodies (dry=true only sizes the workspace) ----------------
+// The row-wise tail of the mel front end on M STFT rows: |STFT|, the mel filterbank, log clamp.
+int mel_from_spec(dcx_codec* h, const float* spec, Act mag, long long M, Act mel, float* loglin, hipStream_t s) {
+  const int nbins = h->cfg.n_fft / 2 + 1;
+  LAUNCH(h, s, "spec_mag", 4.0 * M * nbins, 4.0 * M * (h->dft.cout + h->melfb.cin),
+         dcx::launch_spec_mag(spec, mag.f, mag.p, loglin, M, nbins, h->melfb.cin, s));
+  ConvCall cm = pointwise(mag, M);
+  cm.exact = true;
+  cm.out_to(mel);
+  cm.epi = dcx::EPI_LOGCLAMP;
+  RUN(run_conv(h, h->melfb, cm, s));
+  return DCX_OK;
+}
+
 int stage_mel(dcx_codec* h, const float* audio, int B, int64_t n, Act mel, Bump& ws, hipStream_t s,
               float* loglin = nullptr) {
   const dcx_config& c = h->cfg;
@@ -1226,15 +1252,27 @@ int stage_mel(dcx_codec* h, const float* audio, int B, int64_t n, Act mel, Bump&
   cc.Lq = T;
   cc.y = spec;
   RUN(run_conv(h, h->dft, cc, s));
-  const int nbins = c.n_fft / 2 + 1;
-  LAUNCH(h, s, "spec_mag", 4.0 * B * T * nbins, 4.0 * B * T * (h->dft.cout + h->melfb.cin),
-         dcx::launch_spec_mag(spec, mag.f, mag.p, loglin, (long long)B * T, nbins, h->melfb.cin, s));
-  ConvCall cm = pointwise(mag, (long long)B * T);
-  cm.exact = true;
-  cm.out_to(mel);
-  cm.epi = dcx::EPI_LOGCLAMP;
-  RUN(run_conv(h, h->melfb, cm, s));
-  return DCX_OK;
+  return mel_from_spec(h, spec, mag, (long long)B * T, mel, loglin, s);
+}
+
+// stage_mel on a ragged batch: whole frames [sum T][n_fft] cut per clip (launch_ragged_frames), the DFT
+// as a one-tap GEMM over them (dft1), then the row-wise tail.
+int stage_mel_ragged(dcx_codec* h, const float* audio, const dcx::RaggedSeg& rg, Act mel, Bump& ws, hipStream_t s) {
+  const dcx_config& c = h->cfg;
+  const long long M = rg.rows;
+  Act fr = conv_input(h, ws, (size_t)M * c.n_fft);
+  float* spec = ws.f((size_t)M * h->dft.cout);
+  Act mag = conv_input(h, ws, (size_t)M * h->melfb.cin);
+  if (ws.dry) return DCX_OK;
+  if (!ws.ok()) return fail(h, DCX_ERR_WORKSPACE, "workspace too small for mel");
+  LAUNCH(h, s, "ragged_frames", 0, 10.0 * M * c.n_fft,
+         dcx::launch_ragged_frames(audio, rg, fr.f, fr.p, c.n_fft, c.hop, (c.win - c.hop) / 2, s));
+  ConvCall cc = pointwise(fr, M);
+  cc.exact = true;
+  cc.fixed_tiles = true;
+  cc.y = spec;
+  RUN(run_conv(h, h->dft1, cc, s));
+  return mel_from_spec(h, spec, mag, M, mel, nullptr, s);
 }
 
 // Whether a call may fork its half-batches onto the side stream: a handle with one, not inside a
@@ -1274,13 +1312,26 @@ Act scratch_rows(Act a, long long r0, long long n) {
 
 // The encoder (encoders.py:68-76) on clips of one batch: stem conv + LN, 4 stages of (LN +
 // downsample 1x1 conv) and ConvNeXt blocks, the final LayerNorm into feat.
+// rg: a ragged batch (B = 1, T = its total frames).  The stem then reads the mel rows unfolded per
+// clip into the hidden scratch (free until the first block) as a one-tap GEMM (stem1), and every
+// block's depthwise conv stays inside its clip.
 int encode_clips(dcx_codec* h, const CAct& mel, int B, int T, Act feat, float* xa, float* xb, Act ln, Act hid,
-                 hipStream_t s) {
+                 hipStream_t s, const dcx::RaggedSeg* rg = nullptr) {
   const dcx_config& c = h->cfg;
   const long long M = (long long)B * T;
-  ConvCall cc = framed(mel, B, T, c.n_mels);
-  cc.y = xa;
-  RUN(run_conv(h, h->stem, cc, s));
+  if (rg) {
+    if (!mel.p || !hid.p || mel.c1 || mel.h2) return fail(h, DCX_ERR_STATE, "internal: ragged stem needs planes");
+    LAUNCH(h, s, "ragged_unfold", 0, 6.0 * M * c.n_mels * (1 + h->stem.taps),
+           dcx::launch_ragged_unfold(mel.p, hid.p, *rg, c.n_mels * 6, h->stem.taps, s));
+    ConvCall cc = pointwise(CAct(nullptr, hid.p), M);
+    cc.fixed_tiles = true;
+    cc.y = xa;
+    RUN(run_conv(h, h->stem1, cc, s));
+  } else {
+    ConvCall cc = framed(mel, B, T, c.n_mels);
+    cc.y = xa;
+    RUN(run_conv(h, h->stem, cc, s));
+  }
   RUN(run_ln(h, h->stem_ln, xa, Act{xb, nullptr}, M, s, /*bf16_in=*/true));
   for (int i = 0; i < 4; ++i) {
     if (i > 0) {
@@ -1293,7 +1344,7 @@ int encode_clips(dcx_codec* h, const CAct& mel, int B, int T, Act feat, float* x
       cd.y = xb;
       RUN(run_conv(h, h->ds_conv[i], cd, s));
     }
-    for (auto& bw : h->blocks[i]) RUN(run_block(h, bw, xb, nullptr, B, T, ln, hid, s));
+    for (auto& bw : h->blocks[i]) RUN(run_block(h, bw, xb, nullptr, B, T, ln, hid, s, 0, rg));
   }
   RUN(run_ln(h, h->enc_norm, xb, feat, M, s));  // an h2 feat: row-scaled into feat.row_ash
   return DCX_OK;
@@ -1304,7 +1355,8 @@ int encode_clips(dcx_codec* h, const CAct& mel, int B, int T, Act feat, float* x
 // 354 tiles = 1.38 rounds), so one half's partly filled last round runs beside the other half's
 // launches.  Every kernel computes a clip's rows alone (tiles never span clips; per-row range
 // scales), so the halves give the bits of the whole batch.
-int stage_encode(dcx_codec* h, CAct mel, int B, int T, Act feat, Bump& ws, hipStream_t s) {
+int stage_encode(dcx_codec* h, CAct mel, int B, int T, Act feat, Bump& ws, hipStream_t s,
+                 const dcx::RaggedSeg* rg = nullptr) {
   const dcx_config& c = h->cfg;
   const long long M = (long long)B * T;
   const int cmax = c.enc_dims[3];
@@ -1316,7 +1368,8 @@ int stage_encode(dcx_codec* h, CAct mel, int B, int T, Act feat, Bump& ws, hipSt
   row_ranges(h, ws, M, ln, hid);
   if (ws.dry) return DCX_OK;
   if (!ws.ok()) return fail(h, DCX_ERR_WORKSPACE, "workspace too small for encode");
-  if (B < 2 || !h->knobs.enc_streams || !may_fork(h, s)) return encode_clips(h, mel, B, T, feat, xa, xb, ln, hid, s);
+  if (rg || B < 2 || !h->knobs.enc_streams || !may_fork(h, s))
+    return encode_clips(h, mel, B, T, feat, xa, xb, ln, hid, s, rg);
   const int B0 = (B + 1) / 2;
   const long long r1 = (long long)B0 * T;
   HIPCHK(h, hipEventRecord(h->fork_ev, s));
@@ -1439,7 +1492,7 @@ const unsigned short* decode_table6(const dcx_codec* h) {
 }
 
 int stage_vq_encode(dcx_codec* h, CAct feat, int B, int T, int32_t* codes, float* pin, float* fup, float* quant,
-                    Bump& ws, hipStream_t s) {
+                    Bump& ws, hipStream_t s, const dcx::RaggedSeg* rg = nullptr) {
   const dcx_config& c = h->cfg;
   const long long M = (long long)B * T;
   const int D = c.vq_dim, CD = c.codebook_dim, NC = c.codebook_size;
@@ -1473,7 +1526,7 @@ int stage_vq_encode(dcx_codec* h, CAct feat, int B, int T, int32_t* codes, float
   const bool h2p = X6 && !x6c && takes_h3(h, h->vq_pin);  // project_in on conv_gemm_x3dw
   // the block's output for project_in: compact / planes from its epilogue, or (h3) split per row by
   // the row's exact max afterwards (launch_h2_rows)
-  RUN(run_block(h, h->vq_down_blk, X, h2p ? nullptr : X6, B, T, ln, hid, s, x6c ? 1 : 0));
+  RUN(run_block(h, h->vq_down_blk, X, h2p ? nullptr : X6, B, T, ln, hid, s, x6c ? 1 : 0, rg));
   if (h2p) LAUNCH(h, s, "h2_rows", 0, 8.0 * M * D, dcx::launch_h2_rows(X, X6, M, D, x6_ash, s));
   CAct pin_in(X, X6, x6c);
   pin_in.h2 = h2p;
@@ -1494,7 +1547,7 @@ int stage_vq_encode(dcx_codec* h, CAct feat, int B, int T, int32_t* codes, float
     ConvCall cu = pointwise(zd, M);
     cu.y = quant;
     RUN(run_conv(h, h->vq_up, cu, s));
-    RUN(run_block(h, h->vq_up_blk, quant, nullptr, B, T, ln, hid, s));
+    RUN(run_block(h, h->vq_up_blk, quant, nullptr, B, T, ln, hid, s, 0, rg));
   }
   return DCX_OK;
 }
@@ -1910,6 +1963,68 @@ int encode_clips_to_z(dcx_codec* h, const float* audio, int B, int64_t n, int32_
   RUN(sub([&](Bump& t) { return stage_encode(h, CAct(mel), B, T, feat, t, s); }));
   RUN(sub([&](Bump& t) { return stage_vq_encode(h, CAct(feat), B, T, codes, nullptr, nullptr, nullptr, t, s); }));
   RUN(sub([&](Bump& t) { return stage_vq_decode(h, codes, B, T, z, nullptr, t, s); }));
+  ws.off = need;
+  return DCX_OK;
+}
+
+// ---- ragged batches (dcx_tokenize_ragged) ---------------------------------------------------
+// The plan table (host ints, uploaded by the caller as is): kPlanHead header words, then five prefix
+// arrays of batch + 1 entries (dcx::RaggedSeg).
+constexpr int kPlanMagic = 0x52414731, kPlanHead = 8;
+enum { PLAN_MAGIC = 0, PLAN_BATCH, PLAN_FRAMES, PLAN_SAMPLES, PLAN_T16, PLAN_T4, PLAN_RUN, PLAN_RW };
+constexpr int64_t kRaggedMaxSamples = INT32_MAX, kRaggedMaxFrames = 1 << 20, kRaggedMaxBatch = 1 << 20;
+int64_t plan_words(int64_t batch) { return kPlanHead + 5 * (batch + 1); }
+
+// The segment descriptor of a plan: totals from the host copy, prefix arrays in the device copy.
+bool seg_from_plan(const int32_t* host, const int32_t* dev, int64_t batch, int64_t samples, int64_t frames,
+                   dcx::RaggedSeg& g) {
+  if (host[PLAN_MAGIC] != kPlanMagic || host[PLAN_BATCH] != batch || host[PLAN_FRAMES] != frames ||
+      host[PLAN_SAMPLES] != samples || batch < 1 || batch > kRaggedMaxBatch || frames < batch ||
+      frames > kRaggedMaxFrames)
+    return false;
+  const int64_t n = batch + 1;
+  const int32_t* a = dev + kPlanHead;
+  g.cu_samples = a;
+  g.cu_frames = a + n;
+  g.cu_t16 = a + 2 * n;
+  g.cu_t4 = a + 3 * n;
+  g.cu_run = a + 4 * n;
+  g.batch = (int)batch;
+  g.rows = (int)frames;
+  g.n_t16 = host[PLAN_T16];
+  g.n_t4 = host[PLAN_T4];
+  g.n_run = host[PLAN_RUN];
+  g.rw = host[PLAN_RW];
+  // the work-item counts must be the ones the prefix arrays end with (the kernels' grids)
+  return g.rw == dcx::dwconv_run_rows(frames) && g.n_t16 >= batch && g.n_t16 <= frames && g.n_t4 >= g.n_t16 &&
+         g.n_t4 <= frames && g.n_run >= batch && g.n_run <= frames;
+}
+
+// packed audio -> packed mel -> encoder -> VQ search on the rows of a ragged batch: the stages of
+// encode_clips_to_z on one "clip" of rg.rows rows, the three clip-aware steps segment-aware
+int tokenize_ragged_rows(dcx_codec* h, const float* audio, const dcx::RaggedSeg& rg, int32_t* codes, float* pin,
+                         float* fup, Bump& ws, hipStream_t s) {
+  const dcx_config& c = h->cfg;
+  const long long M = rg.rows;
+  Act mel = conv_input(h, ws, (size_t)M * c.n_mels);
+  Act feat = conv_input(h, ws, (size_t)M * c.enc_dims[3]);
+  feat.c1 = feat.p && takes_compact(h, h->vq_down, M);
+  feat.h2 = feat.p && !feat.c1 && takes_h3(h, h->vq_down);
+  if (x6_mode(h)) feat.row_ash = ws.i((size_t)M);
+  if (feat.h2) feat.r.ash_row = feat.row_ash;
+  const size_t mark = ws.off;
+  size_t need = mark;
+  auto sub = [&](auto fn) -> int {  // each sub-stage reuses the tail of the workspace
+    Bump tail(ws.base, ws.cap, ws.dry);
+    tail.off = mark;
+    int rc = fn(tail);
+    need = std::max(need, tail.off);
+    return rc;
+  };
+  if (!ws.dry && !ws.ok()) return fail(h, DCX_ERR_WORKSPACE, "workspace too small for tokenize_ragged");
+  RUN(sub([&](Bump& t) { return stage_mel_ragged(h, audio, rg, mel, t, s); }));
+  RUN(sub([&](Bump& t) { return stage_encode(h, CAct(mel), 1, (int)M, feat, t, s, &rg); }));
+  RUN(sub([&](Bump& t) { return stage_vq_encode(h, CAct(feat), 1, (int)M, codes, pin, fup, nullptr, t, s, &rg); }));
   ws.off = need;
   return DCX_OK;
 }
@@ -2433,6 +2548,9 @@ static int build_all(dcx_codec* h, Builder& B, int32_t with_generator) {
     h->dft.cin = c.hop; h->dft.cout = N; h->dft.taps = N / c.hop; h->dft.in_step = 1;
     h->dft.w = B.upload(basis);
     h->dft.w6 = B.split_pack(basis, 1, N, N / c.hop, c.hop);
+    h->dft1 = h->dft;  // [Cout][tap * hop + ci] = [Cout][n]: one tap over whole frames
+    h->dft1.cin = N;
+    h->dft1.taps = 1;
     const int kpad = (nb + 31) / 32 * 32;  // even number of 16-deep chunks (x6 kernels step in pairs)
     std::vector<double> fb = mel_fb(nb, c.f_min, c.f_max, c.n_mels, c.sample_rate);
     std::vector<float> pk((size_t)c.n_mels * kpad, 0.f);
@@ -2446,6 +2564,10 @@ static int build_all(dcx_codec* h, Builder& B, int32_t with_generator) {
   {
     const std::string e = "encoder.";
     h->stem = B.conv(e + "downsample_layers.0.0", c.n_mels, c.enc_dims[0], 7, 1, 3);
+    h->stem1 = h->stem;  // one tap over rows unfolded per clip (launch_ragged_unfold)
+    h->stem1.cin = h->stem.taps * h->stem.cin;
+    h->stem1.taps = 1;
+    h->stem1.in_base[0] = 0;
     h->stem_ln = B.ln(e + "downsample_layers.0.1", c.enc_dims[0]);
     for (int i = 0; i < 4; ++i) {
       if (i > 0) {
@@ -2717,6 +2839,81 @@ int dcx_encode_decode(dcx_codec* h, const float* audio, int32_t batch, int64_t n
   if (n <= (h->cfg.win - h->cfg.hop) / 2 || frames_of(h->cfg, n) < 1)
     return fail(h, DCX_ERR_INVALID_ARG, "clip too short for the reflect pad / one STFT frame");
   return stage_encode_decode(h, audio, batch, n, codes, wav, ws, s);
+}
+
+int64_t dcx_ragged_plan_size(int32_t batch) { return batch < 1 ? 0 : plan_words(batch); }
+
+int dcx_ragged_plan(dcx_codec* h, const int64_t* clip_samples, int32_t batch, int32_t* plan, int64_t n_words,
+                    int64_t* total_samples, int64_t* total_frames) {
+  if (!h) return DCX_ERR_INVALID_ARG;
+  if (batch < 1 || batch > kRaggedMaxBatch) return fail(h, DCX_ERR_INVALID_ARG, "ragged plan: batch must be in [1, 2^20]");
+  if (!clip_samples || !plan) return fail(h, DCX_ERR_INVALID_ARG, "ragged plan: null buffer");
+  if (n_words < plan_words(batch))
+    return fail(h, DCX_ERR_INVALID_ARG, "ragged plan: the table holds " + std::to_string(n_words) + " words, " +
+                                            std::to_string(plan_words(batch)) + " needed (dcx_ragged_plan_size)");
+  const int64_t pad = (h->cfg.win - h->cfg.hop) / 2;
+  const int64_t n = (int64_t)batch + 1;
+  int32_t *cs = plan + kPlanHead, *cf = cs + n, *c16 = cf + n, *c4 = c16 + n, *cr = c4 + n;
+  // pass 1: the totals (the run length follows from the total row count)
+  int64_t samples = 0, frames = 0;
+  for (int32_t b = 0; b < batch; ++b) {
+    const int64_t nb = clip_samples[b];
+    if (nb < pad)
+      return fail(h, DCX_ERR_INVALID_ARG, "ragged plan: clip " + std::to_string(b) + " has " + std::to_string(nb) +
+                                              " samples, fewer than the reflect pad's " + std::to_string(pad));
+    if (nb > kRaggedMaxSamples - samples)
+      return fail(h, DCX_ERR_INVALID_ARG, "ragged plan: more than 2^31 - 1 samples in all (at clip " + std::to_string(b) + ")");
+    samples += nb;
+    frames += frames_of(h->cfg, nb + 1);
+    if (frames > kRaggedMaxFrames)
+      return fail(h, DCX_ERR_INVALID_ARG, "ragged plan: more than 2^20 frames in all (at clip " + std::to_string(b) + ")");
+  }
+  const int rw = dcx::dwconv_run_rows(frames);
+  cs[0] = cf[0] = c16[0] = c4[0] = cr[0] = 0;
+  for (int32_t b = 0; b < batch; ++b) {
+    const int64_t T = frames_of(h->cfg, clip_samples[b] + 1);
+    cs[b + 1] = (int32_t)(cs[b] + clip_samples[b]);
+    cf[b + 1] = (int32_t)(cf[b] + T);
+    c16[b + 1] = (int32_t)(c16[b] + (T + 15) / 16);
+    c4[b + 1] = (int32_t)(c4[b] + (T + 3) / 4);
+    cr[b + 1] = (int32_t)(cr[b] + (T + rw - 1) / rw);
+  }
+  plan[PLAN_MAGIC] = kPlanMagic;
+  plan[PLAN_BATCH] = batch;
+  plan[PLAN_FRAMES] = (int32_t)frames;
+  plan[PLAN_SAMPLES] = (int32_t)samples;
+  plan[PLAN_T16] = c16[batch];
+  plan[PLAN_T4] = c4[batch];
+  plan[PLAN_RUN] = cr[batch];
+  plan[PLAN_RW] = rw;
+  if (total_samples) *total_samples = samples;
+  if (total_frames) *total_frames = frames;
+  return DCX_OK;
+}
+
+size_t dcx_ragged_workspace_size(const dcx_codec* h, int32_t batch, int64_t total_frames) {
+  if (!h || batch < 1 || total_frames < batch || total_frames > kRaggedMaxFrames) return 0;
+  dcx::RaggedSeg g{};
+  g.batch = batch;
+  g.rows = (int)total_frames;
+  Bump d(nullptr, 0, true);
+  tokenize_ragged_rows(const_cast<dcx_codec*>(h), nullptr, g, nullptr, nullptr, nullptr, d, 0);
+  return d.off + 4096;
+}
+
+int dcx_tokenize_ragged(dcx_codec* h, const float* audio_packed, const int32_t* plan_dev, const int32_t* plan_host,
+                        int32_t batch, int64_t total_samples, int64_t total_frames, int32_t* codes, float* x_pjt_in,
+                        float* quantized_fup, void* workspace, size_t ws_bytes, void* stream) {
+  STAGE_PRE(false);
+  if (!audio_packed || !plan_dev || !plan_host || !codes) return fail(h, DCX_ERR_INVALID_ARG, "null buffer");
+  if (h->gemm_mode == DCX_GEMM_F32)
+    return fail(h, DCX_ERR_INVALID_ARG, "dcx_tokenize_ragged runs in DCX_GEMM_X6 or DCX_GEMM_BF16 (the packed tensors are planes)");
+  if (h->split_k >= 2)
+    return fail(h, DCX_ERR_STATE, "dcx_tokenize_ragged with split-K on: the partial sums share one scratch region");
+  dcx::RaggedSeg g{};
+  if (!seg_from_plan(plan_host, plan_dev, batch, total_samples, total_frames, g))
+    return fail(h, DCX_ERR_INVALID_ARG, "ragged plan does not match batch / total_samples / total_frames (dcx_ragged_plan)");
+  return tokenize_ragged_rows(h, audio_packed, g, codes, x_pjt_in, quantized_fup, ws, s);
 }
 
 int dcx_module_io(const dcx_codec* h, const char* module, int32_t* in_channels, int32_t* out_channels,

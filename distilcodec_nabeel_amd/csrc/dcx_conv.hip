@@ -4608,13 +4608,13 @@ hipError_t launch_conv(const ConvParams& p, int batch, int phases, hipStream_t s
       return launch_x6w8_af32<256, 32, 4, 1, 64>(p, batch, phases, s);
     }
 #ifndef DCX_NO_DM
-    if (!ks && !h && x6dm_ok(p, false, 256) && big_tiles_pay(p, phases, 256))
+    if (!ks && !h && !p.fixed_tiles && x6dm_ok(p, false, 256) && big_tiles_pay(p, phases, 256))
       return launch_x6dm<0, 256>(p, batch, phases, s, kname);  // x6 1-tap, Cout % 256
 #endif
 #ifndef DCX_NO_PP
     if (p.Cout % 128 == 0 && !h && !b1) return launch_x6pp<0>(p, batch, phases, s, kname);  // x6 1-tap
 #endif
-    const bool dm_b1 = b1 && !h && p.taps == 1 && in_base_nonneg(p) && bf16dm_takes(p.Cin, p.Cout, p.Lq, p.ldx, phases);
+    const bool dm_b1 = b1 && !h && p.taps == 1 && !p.fixed_tiles && in_base_nonneg(p) && bf16dm_takes(p.Cin, p.Cout, p.Lq, p.ldx, phases);
     if (p.x_compact && (!dm_b1 || p.x_compact != 1)) return hipErrorInvalidValue;  // only conv_gemm_bf16dm reads it
 #ifndef DCX_NO_BF16DM
     if (dm_b1) {

@@ -197,6 +197,10 @@ struct ConvParams {
   int gelu_lut;
   // the handle's switches (host only; null = the defaults)
   const Knobs* kn;
+  // host only: the kernel family must not follow the row count Lq, so launch_conv keeps the 256 x 128
+  // tiles where big_tiles_pay would take the 64K-output ones (a ragged batch's one-tap DFT and stem:
+  // a clip's bits must not depend on how many rows share its launch)
+  int fixed_tiles;
   // h3 arithmetic (conv_gemm_x3dq, x_compact == 3: the input in the fp16 "h2" layout of
   // dcx_planes.h): weights [phase][tap][Cin/32][Cout][4 groups][h 8 | l 8] fp16 of w * 2^w3_shift
   const unsigned short* w3;
@@ -386,6 +390,34 @@ bool bf16dm_takes(int cin, int cout, int lq, int ldx, int phases);
 bool vq_bk_takes(int ncodes, int dim);
 // whether vq_prefilter_dm takes the x6-mode search of `rows` rows with x_pjt_in in the "hm" layout
 bool vq_hm_takes(int ncodes, int dim, long long rows);
+// Ragged (packed) batch, dcx_ragged.hip: clip b owns samples [cu_samples[b], cu_samples[b + 1]) of the
+// packed audio (no pad stored) and rows [cu_frames[b], cu_frames[b + 1]) of every [sum T][C] tensor.
+// The dwconv_ln work items never straddle a clip: cu_t16 / cu_t4 count each clip's 16- and 4-row tiles,
+// cu_run its runs of rw rows (rw chosen from the total row count as launch_dwconv_ln chooses it).
+// The five prefix arrays ([batch + 1] ints each) are device pointers into the uploaded plan table; the
+// totals are the host's copy of their last entries.
+struct RaggedSeg {
+  const int *cu_samples, *cu_frames, *cu_t16, *cu_t4, *cu_run;
+  int batch, rw;
+  int rows, n_t16, n_t4, n_run;
+};
+// rows per register-ring run of a dwconv_ln launch of `rows` rows (launch_dwconv_ln's rule)
+inline int dwconv_run_rows(long long rows) {
+  return rows >= 2048LL * 32 ? 32 : rows >= 2048LL * 16 ? 16 : rows >= 2048LL * 8 ? 8 : 4;
+}
+// STFT input of a ragged batch: whole frames [sum T][n_fft] (fp32 and / or planes) of each clip's
+// signal with the reference's leading zero sample and `pad` reflected samples on both sides
+hipError_t launch_ragged_frames(const float* audio, const RaggedSeg& g, float* frames, unsigned short* frames6,
+                                int n_fft, int hop, int pad, hipStream_t s);
+// y[row][j] = x[row + j - taps / 2] for rows of the same clip, zeros beyond the clip's edges; a row of
+// x is row_bytes bytes (a multiple of 16) in any layout whose tap-major concatenation is the layout
+// of [rows][taps * C] (fp32, planes)
+hipError_t launch_ragged_unfold(const void* x, void* y, const RaggedSeg& g, int row_bytes, int taps, hipStream_t s);
+// launch_dwconv_ln on a ragged batch: taps outside the row's own clip are dropped
+hipError_t launch_dwconv_ln_ragged(const float* x, float* y, unsigned short* y6, int y6c, const float* dww,
+                                   const float* dwb, const float* lnw, const float* lnb, const RaggedSeg& g, int C,
+                                   int bf16, const Knobs* kn, hipStream_t s, int* ash_row = nullptr,
+                                   float* amax_row = nullptr);
 hipError_t launch_frame_pad(const float* audio, float* frames, unsigned short* frames6, int batch, long long n, int rows,
                             int hop, int pad_left, hipStream_t s);
 // h2: y6 in the h2 layout (dcx_planes.h) instead of planes

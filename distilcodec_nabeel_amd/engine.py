@@ -106,7 +106,9 @@ class NativeCodec:
         """The workspace of one stage call.  A caller-owned `ws` (e.g. the one a captured hipGraph
         was recorded with) is checked and used as is; otherwise the engine's shared buffer, which
         grows (is reallocated) when a call needs more."""
-        need = self.workspace_size(batch, frames)
+        return self._workspace_of(self.workspace_size(batch, frames), ws)
+
+    def _workspace_of(self, need: int, ws: torch.Tensor | None) -> torch.Tensor:
         if ws is not None:
             if ws.device != self.device or ws.dtype != torch.uint8 or not ws.is_contiguous() or ws.numel() < need:
                 raise ValueError(f"workspace must be a contiguous uint8 tensor on {self.device} of >= {need} bytes")
@@ -248,6 +250,45 @@ class NativeCodec:
             self._check(self.L.dcx_encode_decode(self.h, self._ptr(audio), B, N, self._ptr(codes), self._ptr(wav), self._ptr(ws),
                                                  ws.numel(), self._stream()))
         return codes, wav
+
+    def ragged_plan(self, lengths) -> tuple[np.ndarray, int, int]:
+        """The plan table of a ragged batch (dcx_ragged_plan; host only): (int32 table, total samples,
+        total frames) for clips of `lengths` raw samples.  ValueError names the clip that is too short."""
+        n = np.ascontiguousarray(np.asarray(lengths, dtype=np.int64).reshape(-1))
+        B = int(n.shape[0])
+        words = int(self.L.dcx_ragged_plan_size(B))
+        plan = np.zeros(max(words, 1), dtype=np.int32)
+        ts, tf = ctypes.c_int64(0), ctypes.c_int64(0)
+        self._check(self.L.dcx_ragged_plan(self.h, n.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), B,
+                                           plan.ctypes.data_as(ctypes.c_void_p), words, ctypes.byref(ts), ctypes.byref(tf)))
+        return plan, ts.value, tf.value
+
+    def tokenize_ragged(self, clips, want_pjt_in: bool = False, want_fup: bool = False, ws: torch.Tensor | None = None):
+        """Clips of different lengths (1-D tensors or arrays of raw samples, without the reference's
+        leading zero) -> (codes int32 [sum T], frame_offsets int64 [B + 1] (host), x_pjt_in | None,
+        quantized_fup | None), the last two packed [sum T, codebook_dim].  The clips are packed back to
+        back and tokenized in one call with no padding (dcx_tokenize_ragged); clip b's rows are
+        [frame_offsets[b], frame_offsets[b + 1]) and equal what the clip gives alone."""
+        if len(clips) == 0:
+            raise ValueError("tokenize_ragged needs at least one clip")
+        flat = [torch.as_tensor(c).reshape(-1) for c in clips]
+        lengths = [int(c.numel()) for c in flat]
+        plan, total_samples, total_frames = self.ragged_plan(lengths)
+        B = len(flat)
+        audio = torch.cat([c.to(device=self.device, dtype=torch.float32) for c in flat])
+        plan_dev = torch.from_numpy(plan).to(self.device)
+        offsets = torch.tensor(np.concatenate([[0], np.cumsum([self.num_frames(n + 1) for n in lengths])]), dtype=torch.int64)
+        assert int(offsets[-1]) == total_frames
+        codes = torch.empty(total_frames, dtype=torch.int32, device=self.device)
+        pin = torch.empty(total_frames, self.CD, device=self.device) if want_pjt_in else None
+        fup = torch.empty(total_frames, self.CD, device=self.device) if want_fup else None
+        ws = self._workspace_of(int(self.L.dcx_ragged_workspace_size(self.h, B, total_frames)), ws)
+        with torch.cuda.device(self.device):
+            self._check(self.L.dcx_tokenize_ragged(self.h, self._ptr(audio), self._ptr(plan_dev),
+                                                   plan.ctypes.data_as(ctypes.c_void_p), B, total_samples, total_frames,
+                                                   self._ptr(codes), self._ptr(pin), self._ptr(fup), self._ptr(ws),
+                                                   ws.numel(), self._stream()))
+        return codes, offsets, pin, fup
 
     def module_io(self, name: str) -> tuple[int, int, int]:
         """(input channels, output channels (0: int32 codes), output rows per input row) of a module."""

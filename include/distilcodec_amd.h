@@ -136,6 +136,39 @@ int dcx_generate(dcx_codec* h, const float* z, int32_t batch, int64_t frames, fl
 int dcx_encode_decode(dcx_codec* h, const float* audio, int32_t batch, int64_t n_samples,
                       int32_t* codes, float* wav, void* workspace, size_t ws_bytes, void* stream);
 
+/* Ragged batches: clips of different lengths tokenized in one call with no padding, every clip's
+ * result what dcx_mel -> dcx_encode -> dcx_vq_encode give for that clip ALONE (the reference pads a
+ * batch to its longest clip without masking, distil_codec.py:133-136, so there a clip's last codes
+ * depend on what shares its batch).  Clips are packed back to back: clip b owns samples
+ * [S_b, S_b + n_b) of audio_packed (raw samples; the reference's 1-sample left zero pad is applied
+ * by the kernels, not stored) and rows [F_b, F_b + T_b) of every output, T_b = dcx_num_frames(n_b + 1).
+ * Only the STFT framing, the stem conv and the ConvNeXt blocks' depthwise convs see clip boundaries;
+ * everything else runs on the sum(T_b) rows at once.  The number of kernel launches does not depend
+ * on the number of clips.
+ *
+ * dcx_ragged_plan_size: 32-bit words of the plan table for `batch` clips (0 for batch < 1).
+ * dcx_ragged_plan (host only, no HIP call; any handle, finalized or not): fills the table (opaque:
+ * sample and frame offsets, the per-clip tile and run prefixes of the depthwise-conv kernels) from
+ * the raw clip lengths and returns the totals.  DCX_ERR_INVALID_ARG, with the clip index in
+ * dcx_last_error, for a clip shorter than 384 samples (the reflect pad needs n_b + 1 > 384);
+ * also for batch < 1 or > 2^20, plan_words < dcx_ragged_plan_size(batch), and totals beyond what the
+ * kernels index: more than 2^31 - 1 samples or 2^20 frames (about 3.1 h of audio) in one call.
+ * dcx_ragged_workspace_size: device workspace bytes of dcx_tokenize_ragged (0 for bad arguments).
+ * dcx_tokenize_ragged: the caller uploads the table as is (plan_dev, device; plan_host, the host
+ * copy, is read for the totals).  codes: int32 [sum T]; x_pjt_in / quantized_fup: [sum T][codebook_dim]
+ * or NULL.  Stream-ordered, allocates nothing, never synchronises, and runs on the caller's stream
+ * alone (no half-batch fork).  DCX_GEMM_X6 and DCX_GEMM_BF16; DCX_GEMM_F32 returns DCX_ERR_INVALID_ARG
+ * (the packed intermediates are planes).  DCX_ERR_STATE before dcx_finalize and while split-K is on
+ * (its partial sums share one scratch region).  DCX_ERR_INVALID_ARG when the table does not match
+ * batch / total_samples / total_frames. */
+int64_t dcx_ragged_plan_size(int32_t batch);
+int dcx_ragged_plan(dcx_codec* h, const int64_t* clip_samples, int32_t batch, int32_t* plan, int64_t plan_words,
+                    int64_t* total_samples, int64_t* total_frames);
+size_t dcx_ragged_workspace_size(const dcx_codec* h, int32_t batch, int64_t total_frames);
+int dcx_tokenize_ragged(dcx_codec* h, const float* audio_packed, const int32_t* plan_dev, const int32_t* plan_host,
+                        int32_t batch, int64_t total_samples, int64_t total_frames, int32_t* codes, float* x_pjt_in,
+                        float* quantized_fup, void* workspace, size_t ws_bytes, void* stream);
+
 /* Sample-rate conversion by up/down for input audio at another rate (replaces librosa.resample,
  * distil_codec.py:108-110 and :676, and librosa.load(sr=...) in meldataset.py:18-20).  Polyphase FIR
  * in scipy.signal.resample_poly's form: y[b][i] = sum_m h[(i + pre)*down - up*m] * x[b][m] over the
