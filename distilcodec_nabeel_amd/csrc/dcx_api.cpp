@@ -121,7 +121,6 @@ struct dcx_codec {
   int* vq_stats = nullptr;        // [rows rescored, codes rescored] (dcx_vq_rescore_stats)
   bool vq_stats_on = false;       // counted from the first dcx_vq_rescore_stats call on
   unsigned short* codebook6 = nullptr;
-  unsigned short* codebook_bk = nullptr;  // hi/mid per K32 step (vq_prefilter_bq / _dm; DCX_VQ_OLD builds)
   unsigned short* codebook_b1 = nullptr;  // [CD/32][NC][32] bf16 hi (vq_prefilter_b1)
   unsigned short* ptable6 = nullptr;  // decode table as activation planes (x6 mode gathers)
   // bf16-mode decode table (planes; mid = lo = 0): project_out under autocast, bf16(bf16(E) W16^T + b16)
@@ -130,7 +129,7 @@ struct dcx_codec {
   // fused ResBlock pairs for the C = 32 / 64 generator stages (conv_res_pair); DCX_NO_RESPAIR=1 at
   // dcx_create keeps the per-conv launches (A/B comparisons)
   bool res_pair = true;
-  // compact bf16 activations between bf16-mode producers and conv_gemm_bf16dm / vq_prefilter_bk;
+  // compact bf16 activations between bf16-mode producers and conv_gemm_bf16dm, and x_pjt_in for vq_prefilter_b1;
   // DCX_NO_COMPACT=1 at dcx_create keeps the planes layout (A/B comparisons, same bits)
   bool compact = true;
   // rescore candidate-list capacity per searched row (VqScratch); DCX_VQ_PAIRS_PER_ROW at dcx_create
@@ -610,8 +609,8 @@ int max_gen_width(const dcx_config& c) {  // max over generator layers of channe
 // launches
 // ----------------------------------------------------------------------------------------
 // An activation tensor [rows][C]: fp32 and/or x6 planes ([rows][C/8][3][8] bf16, dcx_planes.h).
-// c1: p holds the compact bf16 layout ([rows][C] hi only; bf16 mode, consumers conv_gemm_bf16dm /
-// vq_prefilter_bk) instead of planes.
+// c1: p holds the compact bf16 layout ([rows][C] hi only; consumers conv_gemm_bf16dm in bf16 mode,
+// vq_prefilter_b1 in either mode) instead of planes.
 // h2: p holds the fp16 "h2" layout ([rows][C/32][8][8] h and l; the h3 generator arithmetic,
 // consumer conv_gemm_x3dq).
 // Range of a tensor (round 6, dcx_kernels.h h2_shift): in the h2 layout it holds x * 2^ash[clip]
@@ -691,7 +690,7 @@ struct ConvCall {
   unsigned short* y6 = nullptr;  // planes of v
   unsigned short* y6s = nullptr; // planes of silu(v)
   bool y6s_h2 = false;           // y6s in the h2 layout
-  int y6c = 0;                   // y6 layout (ConvParams::y_compact): 0 planes, 1 compact bf16, 2 hm, 3 h2
+  int y6c = 0;                   // y6 layout (ConvParams::y_compact): 0 planes, 1 compact bf16, 3 h2 (2 unused)
   float* macc = nullptr;
   const float* res = nullptr;
   const float* gamma = nullptr;
@@ -830,7 +829,7 @@ int conv_params(dcx_codec* h, const ConvW& w, const ConvCall& c, bool force_f32,
   // compact inputs only feed one-product GEMMs; a compact output (the RNE hi value) may also be written
   // in x6 mode (x_pjt_in for vq_prefilter_b1)
   if (p.x_compact == 1 && !one) return fail(h, DCX_ERR_STATE, "internal: compact layout outside bf16 mode");
-  if (p.y_compact == 2 && (!x6 || one)) return fail(h, DCX_ERR_STATE, "internal: hm layout outside x6 mode");
+  if (p.y_compact == 2) return fail(h, DCX_ERR_STATE, "internal: y6 layout 2 is unused");
   if (p.y_compact == 3 && (!x6 || one)) return fail(h, DCX_ERR_STATE, "internal: h2 layout outside x6 mode");
   return DCX_OK;
 }
@@ -1389,23 +1388,12 @@ int stage_encode(dcx_codec* h, CAct mel, int B, int T, Act feat, Bump& ws, hipSt
 }
 
 // x_pjt_in layout the nearest-code search reads (ConvParams::x_compact): 1 compact bf16 for
-// vq_prefilter_b1 (x6 and bf16 modes), else 0 planes (vq_prefilter_x3 / _dm; fp32 mode ignores it).
-// DCX_VQ_OLD builds (A/B): 1 in bf16 mode (vq_prefilter_bq), 2 "hm" in x6 mode (vq_prefilter_dm).
-int vq_xlayout(const dcx_codec* h, long long M) {
-  if (!x6_mode(h) || !h->compact) return 0;
-#ifdef DCX_VQ_OLD
-  if (!h->codebook_bk) return 0;
-  if (h->gemm_mode == DCX_GEMM_BF16) return 1;
-  return dcx::vq_hm_takes(h->cfg.codebook_size, h->cfg.codebook_dim, M) ? 2 : 0;
-#else
-  (void)M;
-  return h->codebook_b1 ? 1 : 0;
-#endif
-}
+// vq_prefilter_b1 (x6 and bf16 modes), else 0 planes (vq_prefilter_dm / _x3; fp32 mode ignores it).
+int vq_xlayout(const dcx_codec* h) { return x6_mode(h) && h->compact && h->codebook_b1 ? 1 : 0; }
 
 // The nearest-code search of DownsampleGRVQ (vector_quantize_pytorch.py:41-45, 496-506; first index on
 // ties) on x_pjt_in P (fp32 [M][CD]) and, in x6 / bf16 mode, P6 in the prefilter's layout xl (0 planes,
-// 1 compact bf16, 2 hm): |x|^2, the certified prefilter and the fp64 rescore (x6 / bf16), or the exact
+// 1 compact bf16): |x|^2, the certified prefilter and the fp64 rescore (x6 / bf16), or the exact
 // fp32 distance GEMM and its reduce (fp32 mode).  pv / pi / pv2: [M][ntiles] scratch, x2: [M].
 // Workspace of one search of M rows: the prefilter's [M][ntiles] partials and, in x6 / bf16 mode, the
 // rescore's candidate list (128 pairs per row on average: the C2 workload lists 62 in x6 mode; a row that does not fit is rescored in place).
@@ -1445,8 +1433,7 @@ int run_vq_search(dcx_codec* h, const float* P, const unsigned short* P6, int xl
   const dcx_config& c = h->cfg;
   const int CD = c.codebook_dim, NC = c.codebook_size;
   const bool x6 = x6_mode(h);
-  const bool p6c = xl == 1, p6hm = xl == 2;
-  const bool b1 = p6c && dcx::vq_b1_takes(NC, CD);
+  const bool b1 = xl == 1 && dcx::vq_b1_takes(NC, CD);
   float* const x2 = v.x2;
   LAUNCH(h, s, "row_sqnorm", 2.0 * M * CD, 4.0 * M * CD,
          dcx::launch_row_sqnorm(P, M, CD, x2, x6 ? v.x2d : nullptr, b1 ? v.xr2 : nullptr, x6 ? v.npairs : nullptr, s));
@@ -1455,8 +1442,8 @@ int run_vq_search(dcx_codec* h, const float* P, const unsigned short* P6, int xl
     p.x = P; p.x6 = P6; p.w = h->codebook; p.w6 = x6 ? h->codebook6 : nullptr;
     p.Cin = CD; p.Cout = NC; p.ldx = CD; p.taps = 1; p.in_step = 1; p.out_mul = 1;
     p.x2 = x2; p.e2 = h->e2; p.part_val = v.pv; p.part_idx = v.pi; p.part_val2 = v.pv2;
-    p.x_compact = p6c ? 1 : p6hm ? 2 : 0;
-    p.wc = b1 ? h->codebook_b1 : p6c || p6hm ? h->codebook_bk : nullptr;
+    p.x_compact = xl;
+    p.wc = b1 ? h->codebook_b1 : nullptr;
     ProfScope ps(h, s);
     const char* kname = "vq";
     if (x6) {
@@ -1497,8 +1484,8 @@ int stage_vq_encode(dcx_codec* h, CAct feat, int B, int T, int32_t* codes, float
   const long long M = (long long)B * T;
   const int D = c.vq_dim, CD = c.codebook_dim, NC = c.codebook_size;
   const bool x6 = x6_mode(h);
-  const int xl = vq_xlayout(h, M);
-  const int ntiles = x6 ? dcx::vq_prefilter_ntiles(NC, CD, M, xl) : dcx::vq_argmin_ntiles(NC);
+  const int xl = vq_xlayout(h);
+  const int ntiles = x6 ? dcx::vq_prefilter_ntiles(NC, CD, xl) : dcx::vq_argmin_ntiles(NC);
   // the down conv's input as the fused pipeline writes it: compact bf16 (bf16 mode) or h2 (h3), the
   // latter scaled per row by the row's exact max as the encoder's final LayerNorm scales it, so the
   // staged and the fused call compute the same bits
@@ -2264,8 +2251,8 @@ int stage_module(dcx_codec* h, const std::string& m, const float* x, int B, int 
     // (vector_quantize_pytorch.py:462-498), x being project_in's bf16 output; row_sqnorm's |x - bf16(x)|^2
     // keeps the prefilter's bound valid for an input that is not bf16-valued.
     const bool x6 = x6_mode(h);
-    const int xl = vq_xlayout(h, M);
-    const int ntiles = x6 ? dcx::vq_prefilter_ntiles(NC, CD, M, xl) : dcx::vq_argmin_ntiles(NC);
+    const int xl = vq_xlayout(h);
+    const int ntiles = x6 ? dcx::vq_prefilter_ntiles(NC, CD, xl) : dcx::vq_argmin_ntiles(NC);
     unsigned short* P6 = x6 ? ws.u16((size_t)M * CD * 3) : nullptr;
     const VqScratch vs = vq_scratch(h, ws, M, ntiles, x6);
     if (ws.dry) return DCX_OK;
@@ -2624,15 +2611,6 @@ static int build_all(dcx_codec* h, Builder& B, int32_t with_generator) {
       }
       h->dmax = std::nextafter((float)(std::sqrt(d2m) * (1.0 + 1e-12)), INFINITY);
       if (dcx::vq_b1_takes(NC, CD)) h->codebook_b1 = B.compact_pack(emb->data, NC, CD);
-#ifdef DCX_VQ_OLD
-      if (dcx::vq_bk_takes(NC, CD)) {
-        h->codebook_bk = (unsigned short*)B.alloc((size_t)NC * CD);  // NC * CD * 2 bf16 (hi, mid)
-        if (!B.bad() && !B.dry &&
-            (dcx::launch_repack_codebook_bk(h->codebook6, NC, CD, h->codebook_bk, 0) != hipSuccess ||
-             hipDeviceSynchronize() != hipSuccess))
-          return fail(h, DCX_ERR_HIP, "bf16 codebook repack failed");
-      }
-#endif
     }
     // decode table: project_out applied to every code once, E * W_out^T + b_out.  Row NC holds
     // project_out(0) = b_out, the row of the reference's masked code -1 (residual_vq.py:120-127:

@@ -483,6 +483,7 @@ __device__ __forceinline__ void epilogue_lds(const ConvParams& p, const ConvPara
         for (int e = 0; e < 8; ++e) xv[e] = x[e >> 2][e & 3];
         if (y6) {
           if (p.y_compact == 1) store_bf16x8(y6, orow, p.Cout, co, xv);
+          // unreachable (run_conv rejects layout 2); kept: removing it moved registers / scratch in other kernels
           else if (p.y_compact == 2) store_hm8(y6, orow, p.Cout, co, xv);
           else if (p.y_compact == 3) store_h2_8<false>(y6, orow, p.Cout, co, xv, rsc);
           else store_planes8(y6, orow, p.Cout, co, xv);
@@ -503,6 +504,7 @@ __device__ __forceinline__ void epilogue_lds(const ConvParams& p, const ConvPara
       } else {
         if (y6) {
           if (p.y_compact == 1) store_bf16x4(y6, orow, p.Cout, co, x[0][0], x[0][1], x[0][2], x[0][3]);
+          // unreachable (run_conv rejects layout 2); kept: removing it moved registers / scratch in other kernels
           else if (p.y_compact == 2) store_hm4(y6, orow, p.Cout, co, x[0][0], x[0][1], x[0][2], x[0][3]);
           else if (p.y_compact == 3) store_h2_4<false>(y6, orow, p.Cout, co, x[0][0], x[0][1], x[0][2], x[0][3], rsc);
           else store_planes4(y6, orow, p.Cout, co, x[0][0], x[0][1], x[0][2], x[0][3]);

@@ -572,18 +572,12 @@ int x3dq_bn(const ConvParams& p) {
 template <int BN>
 hipError_t launch_x3dq(const ConvParams& p, int batch, int phases, hipStream_t s, const char** kname) {
   constexpr int BM = 32768 / BN;
-  const dim3 grid((unsigned)(((p.Lq + BM - 1) / BM) * (p.Cout / BN) * batch * phases));
-  ConvParams q = p;
-  q.batch = batch;
-  q.phases = phases;
   if (p.taps == 1) {
     if (kname) *kname = BN == 256 ? "conv_gemm_x3dm<128,256>" : "conv_gemm_x3dm<256,128>";
-    hipLaunchKernelGGL((conv_gemm_x3dq<BN, 0>), grid, dim3(512), 0, s, q);
-  } else {
-    if (kname) *kname = BN == 256 ? "conv_gemm_x3dq<128,256,halo>" : "conv_gemm_x3dq<256,128,halo>";
-    hipLaunchKernelGGL((conv_gemm_x3dq<BN, 64>), grid, dim3(512), 0, s, q);
+    return launch_flat<BM, BN>(conv_gemm_x3dq<BN, 0>, p, batch, phases, 512, s);
   }
-  return hipGetLastError();
+  if (kname) *kname = BN == 256 ? "conv_gemm_x3dq<128,256,halo>" : "conv_gemm_x3dq<256,128,halo>";
+  return launch_flat<BM, BN>(conv_gemm_x3dq<BN, 64>, p, batch, phases, 512, s);
 }
 
 template hipError_t launch_x3dq<256>(const ConvParams&, int, int, hipStream_t, const char**);
@@ -591,28 +585,20 @@ template hipError_t launch_x3dq<128>(const ConvParams&, int, int, hipStream_t, c
 
 // bsel (x3dq_bn): 384 = the 384 x 128 tiles (the C = 128 stage), 512 = the 256 x 256 tiles
 hipError_t launch_x3dw(const ConvParams& p, int bsel, int batch, int phases, hipStream_t s, const char** kname) {
-  ConvParams q = p;
-  q.batch = batch;
-  q.phases = phases;
   const bool sp = knobs(p).h3_split;
   if (bsel == 384) {
-    const dim3 grid((unsigned)(((p.Lq + 383) / 384) * (p.Cout / 128) * batch * phases));
     if (kname) *kname = "conv_gemm_x3dw<384,128,halo>";
-    if (sp) hipLaunchKernelGGL((conv_gemm_x3dw<64, true, 128>), grid, dim3(512), 0, s, q);
-    else hipLaunchKernelGGL((conv_gemm_x3dw<64, false, 128>), grid, dim3(512), 0, s, q);
-    return hipGetLastError();
+    return sp ? launch_flat<384, 128>(conv_gemm_x3dw<64, true, 128>, p, batch, phases, 512, s)
+              : launch_flat<384, 128>(conv_gemm_x3dw<64, false, 128>, p, batch, phases, 512, s);
   }
-  const dim3 grid((unsigned)(((p.Lq + 255) / 256) * (p.Cout / 256) * batch * phases));
   if (p.taps == 1) {
     if (kname) *kname = "conv_gemm_x3dw<256,256>";
-    if (sp) hipLaunchKernelGGL((conv_gemm_x3dw<0, true>), grid, dim3(512), 0, s, q);
-    else hipLaunchKernelGGL((conv_gemm_x3dw<0, false>), grid, dim3(512), 0, s, q);
-  } else {
-    if (kname) *kname = "conv_gemm_x3dw<256,256,halo>";
-    if (sp) hipLaunchKernelGGL((conv_gemm_x3dw<64, true>), grid, dim3(512), 0, s, q);
-    else hipLaunchKernelGGL((conv_gemm_x3dw<64, false>), grid, dim3(512), 0, s, q);
+    return sp ? launch_flat<256, 256>(conv_gemm_x3dw<0, true>, p, batch, phases, 512, s)
+              : launch_flat<256, 256>(conv_gemm_x3dw<0, false>, p, batch, phases, 512, s);
   }
-  return hipGetLastError();
+  if (kname) *kname = "conv_gemm_x3dw<256,256,halo>";
+  return sp ? launch_flat<256, 256>(conv_gemm_x3dw<64, true>, p, batch, phases, 512, s)
+            : launch_flat<256, 256>(conv_gemm_x3dw<64, false>, p, batch, phases, 512, s);
 }
 
 // bsel 384 / 512: conv_gemm_x3dw_group; 256 / 128: conv_gemm_x3dq_group<bsel>

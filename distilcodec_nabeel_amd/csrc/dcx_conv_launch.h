@@ -11,6 +11,21 @@ inline const Knobs& knobs(const ConvParams& p) {
   return p.kn ? *p.kn : kDefaultKnobs;
 }
 
+// Tiles of a launch over (phase, clip, row tile, column tile), the order flat_tile decodes
+template <int BM, int BN>
+inline long long flat_tiles(const ConvParams& p, int batch, int phases) {
+  return (long long)((p.Lq + BM - 1) / BM) * (p.Cout / BN) * batch * phases;
+}
+// The flat launch: one workgroup of `threads` per BM x BN tile, p with batch / phases set
+template <int BM, int BN, class Kern>
+hipError_t launch_flat(Kern kern, const ConvParams& p, int batch, int phases, int threads, hipStream_t s) {
+  ConvParams q = p;
+  q.batch = batch;
+  q.phases = phases;
+  hipLaunchKernelGGL(kern, dim3((unsigned)flat_tiles<BM, BN>(p, batch, phases)), dim3(threads), 0, s, q);
+  return hipGetLastError();
+}
+
 // dcx_conv_x6w8.hip: conv_gemm_x6w8 (persistent), planes input or (af32) fp32 input split while staging
 template <int BM, int BN, int WM, int WN, int HALO, bool ARGMIN>
 hipError_t launch_x6w8(const ConvParams& p, int batch, int phases, hipStream_t s);
@@ -41,6 +56,7 @@ hipError_t launch_h3_group(const ConvGroup& g, int bsel, bool split, unsigned bl
 #if defined(DCX_CLOCK_DIAG) || defined(DCX_SEG_DIAG) || defined(DCX_TILE_DIAG)
 // each file's DCX_DIAG_FILE (dcx_conv_common.h)
 int diag_conv(int set, unsigned long long* out, int n, int reset);
+int diag_vq(int set, unsigned long long* out, int n, int reset);
 int diag_x6w8(int set, unsigned long long* out, int n, int reset);
 int diag_x6(int set, unsigned long long* out, int n, int reset);
 int diag_h3(int set, unsigned long long* out, int n, int reset);

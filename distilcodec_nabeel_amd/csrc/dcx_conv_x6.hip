@@ -589,18 +589,13 @@ hipError_t launch_x6pp(const ConvParams& p, int batch, int phases, hipStream_t s
   // (BN = 256 needs 128 accumulator + 72 fragment VGPRs and spills at 2 waves per SIMD).  1-tap
   // convs take conv_gemm_x6lm (loads spread through the MFMA segments): 151 -> 161 TF/s at
   // 1024 -> 4096; with a halo it measured equal at k11 and 4-5 % slower at k3 / taps 2.
-  const dim3 grid((unsigned)(((p.Lq + 255) / 256) * (p.Cout / 128) * batch * phases));
-  ConvParams q = p;
-  q.batch = batch;
-  q.phases = phases;
   if constexpr (HALO == 0) {
     if (kname) *kname = "conv_gemm_x6lm<256,128>";
-    hipLaunchKernelGGL((conv_gemm_x6lm<0>), grid, dim3(512), 0, s, q);
+    return launch_flat<256, 128>(conv_gemm_x6lm<0>, p, batch, phases, 512, s);
   } else {
     if (kname) *kname = "conv_gemm_x6pp<256,128,halo>";
-    hipLaunchKernelGGL((conv_gemm_x6pp<HALO, 128>), grid, dim3(512), 0, s, q);
+    return launch_flat<256, 128>(conv_gemm_x6pp<HALO, 128>, p, batch, phases, 512, s);
   }
-  return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1106,38 +1101,21 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_x6dq_group(const ConvGroup g
 
 template <int BN>
 hipError_t launch_x6dq(const ConvParams& p, int batch, int phases, hipStream_t s, const char** kname) {
-  constexpr int BM = 65536 / BN;
-  const dim3 grid((unsigned)(((p.Lq + BM - 1) / BM) * (p.Cout / BN) * batch * phases));
-  ConvParams q = p;
-  q.batch = batch;
-  q.phases = phases;
   if (kname) *kname = BN == 256 ? "conv_gemm_x6dq<256,256,halo>" : "conv_gemm_x6dq<512,128,halo>";
-  hipLaunchKernelGGL((conv_gemm_x6dq<BN>), grid, dim3(512), 0, s, q);
-  return hipGetLastError();
+  return launch_flat<65536 / BN, BN>(conv_gemm_x6dq<BN>, p, batch, phases, 512, s);
 }
 
 template <int HALO, int BN>
 hipError_t launch_x6dm(const ConvParams& p, int batch, int phases, hipStream_t s, const char** kname) {
-  constexpr int BM = 65536 / BN;
-  const dim3 grid((unsigned)(((p.Lq + BM - 1) / BM) * (p.Cout / BN) * batch * phases));
-  ConvParams q = p;
-  q.batch = batch;
-  q.phases = phases;
   if (kname)
     *kname = BN == 256 ? (HALO ? "conv_gemm_x6dm<256,256,halo>" : "conv_gemm_x6dm<256,256>") : "conv_gemm_x6dm<512,128,halo>";
-  hipLaunchKernelGGL((conv_gemm_x6dm<HALO, BN>), grid, dim3(512), 0, s, q);
-  return hipGetLastError();
+  return launch_flat<65536 / BN, BN>(conv_gemm_x6dm<HALO, BN>, p, batch, phases, 512, s);
 }
 
 // x6 with an fp32 input at Cout = 64: ping-pong, 512 x 64 tiles
 hipError_t launch_x6pf(const ConvParams& p, int batch, int phases, hipStream_t s, const char** kname) {
   if (kname) *kname = "conv_gemm_x6pf<512,64,halo>";
-  ConvParams q = p;
-  q.batch = batch;
-  q.phases = phases;
-  hipLaunchKernelGGL((conv_gemm_x6pp<64, 64, true>), dim3((unsigned)(((p.Lq + 511) / 512) * (p.Cout / 64) * batch * phases)),
-                     dim3(512), 0, s, q);
-  return hipGetLastError();
+  return launch_flat<512, 64>(conv_gemm_x6pp<64, 64, true>, p, batch, phases, 512, s);
 }
 
 hipError_t launch_x6dq_group(const ConvGroup& g, int bn, unsigned blocks, hipStream_t s, const char** kname) {

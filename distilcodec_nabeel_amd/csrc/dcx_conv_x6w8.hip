@@ -340,7 +340,7 @@ static hipError_t launch_x6_persistent(ConvParams p, int batch, int phases, hipS
   const int resident = device_cus() * per_cu;
   p.batch = batch;
   p.phases = phases;
-  const long long total = (long long)((p.Lq + BM - 1) / BM) * (p.Cout / BN) * batch * phases;
+  const long long total = flat_tiles<BM, BN>(p, batch, phases);
   if (total > (1LL << 30)) return hipErrorInvalidValue;
   int g = (int)std::min<long long>(resident, (total + 7) / 8 * 8);
   g = std::max(8, g / 8 * 8);

@@ -175,14 +175,13 @@ struct ConvParams {
   // only the fp32 tensor, not its silu as well)
   int silu_in;
   // Layouts other than planes for x6 / y6 (dcx_planes.h), 0 = planes:
-  //   1 = compact bf16 ([rows][C], hi plane only; bf16 mode; read by conv_gemm_bf16dm and
-  //       vq_prefilter_bk; written with round_bf16, ldy == Cout);
-  //   2 = "hm" ([rows][C/32][8][8], hi and mid planes per 32 channels; x6-mode x_pjt_in, read by
-  //       vq_prefilter_dm only);
-  //   3 = "h2" (x only: [rows][C/32][8][8] fp16 h and l per 32 channels; read by conv_gemm_x3dq).
+  //   1 = compact bf16 ([rows][C], hi plane only; read by conv_gemm_bf16dm (bf16 mode) and
+  //       vq_prefilter_b1 (x_pjt_in, either mode); ldy == Cout);
+  //   3 = "h2" ([rows][C/32][8][8] fp16 h and l per 32 channels; read by the h3 kernels).
+  // 2 is unused.
   int x_compact, y_compact;
   // bf16-mode 1x1 weights as [phase][Cin/32][Cout][32] bf16 (hi only; conv_gemm_bf16dm), or null;
-  // for the VQ prefilter: the codebook as launch_repack_codebook_bk writes it.
+  // for vq_prefilter_b1: the codebook in the same layout (compact_pack, dcx_api.cpp).
   const unsigned short* wc;
   // split-K (conv_gemm_x6pp / x6lm only): ksplit > 1 slices over input-channel chunks, each a
   // whole number of kunit chunks; batch = clips * ksplit, and slice s of clip c is output clip
@@ -302,16 +301,14 @@ hipError_t launch_splitk_epilogue_group(const ConvParams* ps, const float* const
                                         const long long* strides, int n, int batch, bool chain, hipStream_t s);
 hipError_t launch_vq_argmin(const ConvParams& p, int rows, hipStream_t s, const char** kname);
 int vq_argmin_ntiles(int ncodes);
-// per-row partial count of the x6 / bf16-mode prefilter launch_vq_prefilter runs for `rows` rows with
-// x_pjt_in in layout x_layout (ConvParams::x_compact)
-int vq_prefilter_ntiles(int ncodes, int dim, long long rows, int x_layout);
-// VQ search, x6 mode: bf16x3 prefilter (approximate squared distances, per-tile top 2) ...
-// x_bf16: the rows of x are bf16 values (mid and lo planes zero), which drops the mid*hi product.
-// p.x_compact == 1 (bf16 mode) / 2 (x6 mode, "hm" layout) with p.wc the launch_repack_codebook_bk
-// codebook: vq_prefilter_bk / vq_prefilter_dm reading contiguous runs.
+// per-row partial count of the prefilter launch_vq_prefilter runs with x_pjt_in in layout x_layout
+// (ConvParams::x_compact: 0 planes, 1 compact bf16)
+int vq_prefilter_ntiles(int ncodes, int dim, int x_layout);
+// VQ search, x6 / bf16 mode: prefilter (approximate squared distances, per-tile top 2) ...
 // p.x_compact == 1 with p.wc the [CD/32][NC][32] bf16 hi codebook: vq_prefilter_b1 (one product,
-// both modes; vq_b1_takes).  Built with -DDCX_VQ_OLD (A/B): p.x_compact == 1 (bf16 mode) / 2 (x6
-// mode, "hm" layout) with p.wc the launch_repack_codebook_bk codebook: vq_prefilter_bq / _dm.
+// both modes; vq_b1_takes).  p.x_compact == 0 (planes, p.w6 the planes codebook): vq_prefilter_dm
+// or, where its shape limits fail, vq_prefilter_x3 (three products); x_bf16: the rows of x are bf16
+// values (mid and lo planes zero), which drops the mid*hi product.
 hipError_t launch_vq_prefilter(const ConvParams& p, int rows, bool x_bf16, hipStream_t s, const char** kname);
 bool vq_b1_takes(int ncodes, int dim);
 // ... then per row: certify the prefilter's winner with a rigorous error bound, or rescore every
@@ -381,15 +378,8 @@ hipError_t launch_zero_words(void* p, long long n, hipStream_t s);
 hipError_t launch_clip_amax(const float* x, int batch, long long L, int C, float* amax, hipStream_t s);
 // the CU count of the current device (cached per device, thread-safe)
 int device_cus();
-// x6 codebook planes -> the per-K32 hi/mid layout of vq_prefilter_bk ((dim / 32) * ncodes * 64 bf16)
-hipError_t launch_repack_codebook_bk(const unsigned short* cb6, int ncodes, int dim, unsigned short* out,
-                                     hipStream_t s);
 // whether conv_gemm_bf16dm takes a one-tap conv of this shape (then its input may be compact)
 bool bf16dm_takes(int cin, int cout, int lq, int ldx, int phases);
-// whether vq_prefilter_bk takes the bf16-mode search (then x_pjt_in may be compact)
-bool vq_bk_takes(int ncodes, int dim);
-// whether vq_prefilter_dm takes the x6-mode search of `rows` rows with x_pjt_in in the "hm" layout
-bool vq_hm_takes(int ncodes, int dim, long long rows);
 // Ragged (packed) batch, dcx_ragged.hip: clip b owns samples [cu_samples[b], cu_samples[b + 1]) of the
 // packed audio (no pad stored) and rows [cu_frames[b], cu_frames[b + 1]) of every [sum T][C] tensor.
 // The dwconv_ln work items never straddle a clip: cu_t16 / cu_t4 count each clip's 16- and 4-row tiles,

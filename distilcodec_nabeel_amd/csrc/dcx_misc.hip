@@ -465,13 +465,12 @@ __global__ void __launch_bounds__(256) split_planes_kernel(const float* __restri
     const f32x4 v = *reinterpret_cast<const f32x4*>(x + i4 * 4);
     const long long i = i4 * 4;
     if (compact == 1) store_bf16x4(y6, i / C, C, (int)(i % C), v.x, v.y, v.z, v.w);
-    else if (compact == 2) store_hm4(y6, i / C, C, (int)(i % C), v.x, v.y, v.z, v.w);
     else store_planes4(y6, i / C, C, (int)(i % C), v.x, v.y, v.z, v.w);
   }
 }
 
 hipError_t launch_split_planes(const float* x, unsigned short* y6, long long rows, int C, int compact, hipStream_t s) {
-  if (C % 8 || compact < 0 || compact > 2 || (compact >= 2 && C % 32)) return hipErrorInvalidValue;
+  if (C % 8 || compact < 0 || compact > 1) return hipErrorInvalidValue;
   const long long total4 = rows * C / 4;
   unsigned g = (unsigned)((total4 + 255) / 256);
   if (g > 8192) g = 8192;
@@ -1019,33 +1018,6 @@ hipError_t launch_resample_poly(const float* x, int batch, long long n_in, long 
                                 hipStream_t s) {
   const dim3 grid((unsigned)((n_out + 255) / 256), (unsigned)batch);
   hipLaunchKernelGGL(resample_poly_kernel, grid, dim3(256), 0, s, x, n_in, xs, h, hlen, up, down, pre, y, n_out, ys);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------
-// Codebook for the bf16-mode VQ prefilter (vq_prefilter_bk): the hi and mid planes of the x6
-// codebook ([CD/16][NC][2 halves][3 planes][8], ConvParams::w6 layout) repacked per K32 step as
-// [CD/32][NC][8 pieces][8] bf16, piece = (chunk half cc, channel half hh, plane hi/mid) =
-// (cc * 2 + hh) * 2 + pl: 128 contiguous bytes per code per step.  One thread per 16-byte piece.
-// ---------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) repack_codebook_bk_kernel(const unsigned short* __restrict__ cb6, int ncodes,
-                                                                 long long pieces, unsigned short* __restrict__ out) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= pieces) return;
-  const int pc = (int)(i & 7);
-  const long long sn = i >> 3;  // step * ncodes + code
-  const long long st = sn / ncodes, n = sn - st * ncodes;
-  const int cc = pc >> 2, hh = (pc >> 1) & 1, pl = pc & 1;
-  const unsigned short* src = cb6 + ((2 * st + cc) * ncodes + n) * 48 + hh * 24 + pl * 8;
-  *reinterpret_cast<uint4*>(out + i * 8) = *reinterpret_cast<const uint4*>(src);
-}
-
-hipError_t launch_repack_codebook_bk(const unsigned short* cb6, int ncodes, int dim, unsigned short* out,
-                                     hipStream_t s) {
-  if (dim % 32) return hipErrorInvalidValue;
-  const long long pieces = (long long)(dim / 32) * ncodes * 8;
-  hipLaunchKernelGGL(repack_codebook_bk_kernel, dim3((unsigned)((pieces + 255) / 256)), dim3(256), 0, s, cb6, ncodes,
-                     pieces, out);
   return hipGetLastError();
 }
 

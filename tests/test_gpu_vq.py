@@ -121,8 +121,9 @@ def test_workspace_without_generator(veng):
 
 def test_compact_layout_same_codes(veng, cfg, state):
     """x6 mode hands x_pjt_in to vq_prefilter_b1 in the compact bf16 layout with the codebook's hi
-    plane packed per K32 step; DCX_NO_COMPACT=1 keeps the planes layout (vq_prefilter_x3). Both
-    searches are exact, so x_pjt_in and the codes agree bit for bit."""
+    plane packed per K32 step; DCX_NO_COMPACT=1 keeps the planes layout, which at the shipped
+    codebook (32768 x 3584, inside vq_prefilter_dm's shape limits) runs vq_prefilter_dm, not the
+    vq_prefilter_x3 fallback. Both searches are exact, so x_pjt_in and the codes agree bit for bit."""
     import os
 
     from distilcodec_nabeel_amd.engine import NativeCodec
