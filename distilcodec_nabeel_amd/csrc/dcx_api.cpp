@@ -1285,6 +1285,10 @@ bool may_fork(dcx_codec* h, hipStream_t s) {
 
 // Rows [r0, ...) (clips b0 on) of a [B][T][C] activation in its layout (planes 3, h2 2, compact 1
 // ushorts per element), with its per-row and per-clip range pointers.
+// The three a.r offsets are unreached today, so no test exercises them: the activations that are split
+// carry no consumer-side ranges (mel has none, feat's consumer reads the whole batch's table through
+// the unsplit Act, z carries none).  The live offsets of a split are the producer-side row_ash /
+// row_amax in act_rows_out and scratch_rows.
 template <class A>
 A act_rows(A a, int b0, long long r0, long long C) {
   if (a.f) a.f += r0 * C;

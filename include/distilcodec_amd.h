@@ -215,7 +215,8 @@ int dcx_transpose(const float* in, float* out, int32_t batch, int64_t rows, int6
  *               inputs) saturates and sets a flag (dcx_range_flags).
  *               Both forms are held to the fp32 tolerance of the product contract (tests/test_gpu_h3.py,
  *               tests/test_gpu_range.py: module outputs within 2e-4 relative of fp64 at input scales
- *               2^-12 .. 2^12); neither is IEEE fp32 arithmetic (that is DCX_GEMM_F32);
+ *               2^-12 .. 2^12; tests/test_gpu_mixed_scale.py: the same per clip and per row on batches
+ *               whose clips and rows differ in scale); neither is IEEE fp32 arithmetic (that is DCX_GEMM_F32);
  *  DCX_GEMM_F32 v_mfma_f32_32x32x2_f32 (IEEE fp32 fma chain);
  *  DCX_GEMM_BF16 the reference's enable_bfloat16 (torch.autocast bf16, distil_codec.py:550): conv /
  *               linear operands rounded to bf16, one bf16 product, fp32 accumulation, results

@@ -18,6 +18,39 @@ def snr_db(x, ref) -> float:
     return float(10 * np.log10((ref ** 2).sum() / max(((x - ref) ** 2).sum(), 1e-300)))
 
 
+def _f64(x):
+    return np.asarray(x.detach().cpu() if torch.is_tensor(x) else x, np.float64)
+
+
+def rel_per_clip(y, ref) -> np.ndarray:
+    """max|y_b - ref_b| / max|ref_b| for every clip b (axis 0): shape (B,).  A batch-wide
+    max|err| / max|ref| is carried by the loudest clip: a quiet clip that is entirely wrong beside
+    it changes nothing there, and reads 1.0 here."""
+    y, ref = _f64(y), _f64(ref)
+    assert y.shape == ref.shape, (y.shape, ref.shape)
+    B = ref.shape[0]
+    err = np.abs(y - ref).reshape(B, -1).max(axis=1)
+    return err / (np.abs(ref).reshape(B, -1).max(axis=1) + 1e-300)
+
+
+def rel_per_row(y, ref, channel_axis: int = 1) -> np.ndarray:
+    """The same per (clip, row) of a (B, C, L) tensor (channels_first as the oracle lays it out;
+    channel_axis=2 for channels-last), the maxima taken over the channels: shape (B, L)."""
+    y, ref = _f64(y), _f64(ref)
+    assert y.shape == ref.shape and y.ndim == 3, (y.shape, ref.shape)
+    return np.abs(y - ref).max(axis=channel_axis) / (np.abs(ref).max(axis=channel_axis) + 1e-300)
+
+
+def snr_per_clip(y, ref) -> np.ndarray:
+    """SNR in dB of every clip (axis 0) against its own reference: shape (B,)."""
+    y, ref = _f64(y), _f64(ref)
+    assert y.shape == ref.shape, (y.shape, ref.shape)
+    B = ref.shape[0]
+    sig = (ref ** 2).reshape(B, -1).sum(axis=1)
+    noise = ((y - ref) ** 2).reshape(B, -1).sum(axis=1)
+    return 10 * (np.log10(np.maximum(sig, 1e-300)) - np.log10(np.maximum(noise, 1e-300)))
+
+
 def check_codes(gpu_codes, ref_codes, decisive, min_match: float = 0.97) -> float:
     """Exact on decisive frames, >= min_match exact overall; returns the exact-match rate."""
     gc = np.asarray(gpu_codes.cpu() if torch.is_tensor(gpu_codes) else gpu_codes).astype(np.int64)
