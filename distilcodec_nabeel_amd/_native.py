@@ -104,6 +104,9 @@ SIGNATURES = {
     "dcx_conv_create": (ctypes.c_int, [_P, _P, _I32, _I32, _I32, _I32, _I32, _I32, ctypes.POINTER(_P)]),
     "dcx_conv_forward": (ctypes.c_int, [_P, _I32, _P, _I32, _I64, _P, _P, _P, _I32, _P]),
     "dcx_conv_destroy": (None, [_P]),
+    "dcx_conv_last_kernel": (ctypes.c_char_p, [_P]),
+    "dcx_conv_set_knob": (ctypes.c_int, [_P, ctypes.c_char_p, _I32]),
+    "dcx_conv_set_h3": (ctypes.c_int, [_P, _I32]),
     "dcx_module_workspace_size": (_SZ, [_P, ctypes.c_char_p, _I32, _I64]),
     "dcx_module_io": (ctypes.c_int, [_P, ctypes.c_char_p, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
     "dcx_module_forward": (ctypes.c_int, [_P, ctypes.c_char_p, _P, _I32, _I64, _I32, _P, _P, _SZ, _P]),

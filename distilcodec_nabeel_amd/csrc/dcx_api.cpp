@@ -156,6 +156,8 @@ struct dcx_codec {
   float* post_w = nullptr;
   float post_b = 0.f;
 
+  const char* last_kname = "";  // the kernel run_conv launched last (dcx_conv_last_kernel)
+
   bool prof = false;
   std::vector<hipEvent_t> events;
   int ev_used = 0;
@@ -915,6 +917,7 @@ int run_conv_split(dcx_codec* h, const ConvW& w, const ConvCall& c, const ConvPa
   q.y_amax = nullptr;
   const char* kname = "conv";
   HIPCHK(h, dcx::launch_conv(q, c.batch * S, w.phases, s, &kname));
+  h->last_kname = kname;
   HIPCHK(h, dcx::launch_splitk_epilogue(p, h->split_buf, S, (long long)c.batch * p.y_bstride, c.batch, w.phases, s));
   ps.done((std::string("splitk:") + kname).c_str(), conv_flops(w, c), conv_bytes(w, c));
   return DCX_OK;
@@ -948,6 +951,7 @@ int run_conv(dcx_codec* h, const ConvW& w, const ConvCall& c, hipStream_t s, boo
   ProfScope ps(h, s);
   const char* kname = "conv";
   HIPCHK(h, dcx::launch_conv(p, c.batch, w.phases, s, &kname));
+  h->last_kname = kname;
   ps.done(kname, conv_flops(w, c), conv_bytes(w, c));
   return DCX_OK;
 }
@@ -3004,8 +3008,11 @@ int dcx_range_flags(dcx_codec* h, int32_t* flags, int32_t reset) {
 struct dcx_conv {
   dcx_codec scratch;  // owns the device allocations and the last error
   ConvW w;
-  unsigned short* planes = nullptr;  // x6 input planes of the last call (grown on demand)
+  unsigned short* planes = nullptr;  // x6 input planes (or the h2 layout) of the last call (grown on demand)
   size_t planes_cap = 0;
+  bool h3 = false;         // dcx_conv_set_h3: h3 arithmetic where the stages would use it
+  int* range = nullptr;    // h3: per-clip max |x| [batch], then the clips' or rows' shifts
+  size_t range_cap = 0;    // words
 };
 
 extern "C" {
@@ -3029,7 +3036,9 @@ int dcx_conv_create(const float* weight, const float* bias, int32_t cin, int32_t
   if (bias) bt.data.assign(bias, bias + cout); else bt.data.assign(cout, 0.f);
   h->host["c.bias"] = bt;
   Builder B{h, false};
-  c->w = transposed ? B.convT("c", cin, cout, k, stride) : B.conv("c", cin, cout, k, dilation, dilation * (k - 1) / 2);
+  // (the h3 weights too: dcx_conv_set_h3 may switch them on later)
+  c->w = transposed ? B.convT("c", cin, cout, k, stride, true)
+                    : B.conv("c", cin, cout, k, dilation, dilation * (k - 1) / 2, true, true);
   h->host.clear();
   if (B.bad()) {
     int code = B.e.code;
@@ -3059,7 +3068,36 @@ int dcx_conv_forward(dcx_conv* c, int32_t gemm_mode, const float* x, int32_t bat
       if (hipMalloc(&c->planes, need * sizeof(unsigned short)) != hipSuccess) return DCX_ERR_OOM;
       c->planes_cap = need;
     }
-    if (dcx::launch_split_planes(x, c->planes, (long long)batch * lin, c->w.cin, 0, s) != hipSuccess) return DCX_ERR_HIP;
+    // h3 (dcx_conv_set_h3): the input in the h2 layout, range-scaled as ensure_planes does for a
+    // caller's tensor: per clip (exact max) for the tap convs, per row for a one-tap Conv1d
+    const bool h3 = c->h3 && (c->w.taps >= 2 ? takes_h3_conv(h, c->w, lin) : takes_h3(h, c->w));
+    if (h3) {
+      const long long rows = (long long)batch * lin;
+      const size_t words = (size_t)batch + (size_t)std::max<long long>(batch, rows);
+      if (words > c->range_cap) {
+        if (c->range) hipFree(c->range);
+        c->range = nullptr;
+        c->range_cap = 0;
+        if (hipMalloc(&c->range, words * sizeof(int)) != hipSuccess) return DCX_ERR_OOM;
+        c->range_cap = words;
+      }
+      float* am = reinterpret_cast<float*>(c->range);
+      int* ash = c->range + batch;
+      xa.r = Rng{};
+      if (c->w.taps >= 2) {
+        if (dcx::launch_h2_ranged(x, nullptr, c->planes, batch, lin, c->w.cin, 0, 0.f, am, ash, h->rflag, s) != hipSuccess)
+          return fail(h, DCX_ERR_HIP, "h3 input split (per clip) failed");
+        xa.r.ash = ash;
+        xa.r.amax = am;
+      } else {
+        if (dcx::launch_h2_rows(x, c->planes, rows, c->w.cin, ash, s) != hipSuccess)
+          return fail(h, DCX_ERR_HIP, "h3 input split (per row) failed: Cin must be 256, 512, 768 or 1024");
+        xa.r.ash_row = ash;
+      }
+      xa.h2 = true;
+    } else if (dcx::launch_split_planes(x, c->planes, (long long)batch * lin, c->w.cin, 0, s) != hipSuccess) {
+      return DCX_ERR_HIP;
+    }
     xa.p = c->planes;
   }
   ConvCall cc = framed(xa, batch, (int)lin, c->w.cin);
@@ -3073,8 +3111,25 @@ int dcx_conv_forward(dcx_conv* c, int32_t gemm_mode, const float* x, int32_t bat
 void dcx_conv_destroy(dcx_conv* c) {
   if (!c) return;
   if (c->planes) hipFree(c->planes);
+  if (c->range) hipFree(c->range);
   for (void* p : c->scratch.allocs) hipFree(p);
   delete c;
+}
+
+const char* dcx_conv_last_kernel(const dcx_conv* c) { return c ? c->scratch.last_kname : ""; }
+
+int dcx_conv_set_knob(dcx_conv* c, const char* name, int32_t value) {
+  if (!c || !name) return DCX_ERR_INVALID_ARG;
+  int* k = knob_slot(c->scratch.knobs, name);
+  if (!k) return fail(&c->scratch, DCX_ERR_INVALID_ARG, std::string("unknown knob: ") + name);
+  *k = value;
+  return DCX_OK;
+}
+
+int dcx_conv_set_h3(dcx_conv* c, int32_t on) {
+  if (!c) return DCX_ERR_INVALID_ARG;
+  c->h3 = on != 0;
+  return DCX_OK;
 }
 
 int dcx_profile_enable(dcx_codec* h, int32_t on) {

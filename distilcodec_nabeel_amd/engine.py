@@ -359,9 +359,12 @@ class NativeCodec:
 
 class NativeConv:
     """The conv primitive of libdcx (dcx_conv_*): Conv1d ("same" padding, dilation) or
-    ConvTranspose1d (padding (k-stride)/2) on channels-last fp32 tensors."""
+    ConvTranspose1d (padding (k-stride)/2) on channels-last fp32 tensors.  h3=True: in gemm="x6", convs
+    the stages would run in h3 arithmetic take the h3 kernels (dcx_conv_set_h3); last_kernel names the
+    kernel the last call launched."""
 
-    def __init__(self, weight: np.ndarray, bias=None, dilation: int = 1, transposed: bool = False, stride: int = 1):
+    def __init__(self, weight: np.ndarray, bias=None, dilation: int = 1, transposed: bool = False, stride: int = 1,
+                 h3: bool = False):
         self.L = _native.lib()
         w = np.ascontiguousarray(weight, dtype=np.float32)
         if transposed:
@@ -377,6 +380,18 @@ class NativeConv:
         if rc != _native.DCX_OK:
             raise ValueError(f"dcx_conv_create failed: {self.L.dcx_status_string(rc).decode()}")
         self.h = h
+        if h3 and self.L.dcx_conv_set_h3(self.h, 1) != _native.DCX_OK:
+            raise ValueError("dcx_conv_set_h3 failed")
+
+    def set_knob(self, name: str, value: int):
+        """An A/B switch of the primitive's own handle (dcx_conv_set_knob), e.g. DCX_H3_BN."""
+        rc = self.L.dcx_conv_set_knob(self.h, name.encode(), int(value))
+        if rc != _native.DCX_OK:
+            raise _native.NativeError(rc, f"dcx_conv_set_knob({name}) failed")
+
+    @property
+    def last_kernel(self) -> str:
+        return self.L.dcx_conv_last_kernel(self.h).decode()
 
     def __del__(self):
         h = getattr(self, "h", None)

@@ -276,6 +276,18 @@ int dcx_conv_create(const float* weight, const float* bias, int32_t cin, int32_t
 int dcx_conv_forward(dcx_conv* c, int32_t gemm_mode, const float* x, int32_t batch, int64_t lin, float* y,
                      float* y_silu, const float* res, int32_t epi, void* stream);
 void dcx_conv_destroy(dcx_conv* c);
+/* dcx_conv_last_kernel: the profile name of the kernel the last dcx_conv_forward launched (the name
+ * dcx_profile_read reports for the stages; "" before the first call), so a test can assert which
+ * kernel a shape reaches.  The string is static.
+ * dcx_conv_set_knob: dcx_set_knob for the primitive's own handle (DCX_H3_BN, DCX_H3_SPLIT, ...).
+ * dcx_conv_set_h3 (default off): in DCX_GEMM_X6, a conv the stages would run in h3 arithmetic (a tap
+ * conv or ConvTranspose with Cout % 128 == 0 and Cin % 32 == 0; a one-tap Conv1d likewise, with Cin
+ * 256, 512, 768 or 1024) runs on the h3 kernels: the input is split into the h2 layout with each clip's
+ * exact range (one-tap: each row's), as the stages do for a caller's tensor.  Other convs and modes
+ * are not affected.  Accuracy: the h3 contract of DCX_GEMM_X6 (2e-4 of the output's max). */
+const char* dcx_conv_last_kernel(const dcx_conv* c);
+int dcx_conv_set_knob(dcx_conv* c, const char* name, int32_t value);
+int dcx_conv_set_h3(dcx_conv* c, int32_t on);
 
 /* Single reference modules, for per-module parity tests (tests/test_gpu_modules.py against the
  * reference's own module outputs, tests/golden/modules.npz and bf16.npz).  `module` is the module's

@@ -240,6 +240,16 @@ static int run_abi(const char* specs_path) {
   CHECK(dcx_conv_create(w.data(), nullptr, 30, 64, 3, 1, 0, 1, &cv) == DCX_ERR_INVALID_ARG);  // cin % 16
   const int rc = dcx_conv_create(w.data(), nullptr, 32, 64, 3, 1, 0, 1, &cv);
   CHECK(gpu ? rc == DCX_OK : rc != DCX_OK);
+  CHECK(dcx_conv_set_h3(nullptr, 1) == DCX_ERR_INVALID_ARG);
+  CHECK(dcx_conv_set_knob(nullptr, "DCX_H3_BN", 128) == DCX_ERR_INVALID_ARG);
+  CHECK(std::strcmp(dcx_conv_last_kernel(nullptr), "") == 0);
+  if (cv) {
+    CHECK(dcx_conv_set_h3(cv, 1) == DCX_OK);
+    CHECK(dcx_conv_set_knob(cv, "DCX_H3_BN", 128) == DCX_OK);
+    CHECK(dcx_conv_set_knob(cv, "DCX_NOT_A_KNOB", 1) == DCX_ERR_INVALID_ARG);
+    CHECK(dcx_conv_set_knob(cv, nullptr, 1) == DCX_ERR_INVALID_ARG);
+    CHECK(std::strcmp(dcx_conv_last_kernel(cv), "") == 0);  // no call yet
+  }
   if (cv) dcx_conv_destroy(cv);
   double taps[8] = {0};
   CHECK(dcx_resample_poly(nullptr, 1, 10, 10, taps, 8, 1, 2, 0, nullptr, 5, 5, nullptr) != DCX_OK);

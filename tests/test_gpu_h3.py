@@ -218,3 +218,64 @@ def test_generator_h3_pairs_vs_x6(eng, golden):
     s36, s3r = _snr(w3, w6), _snr(w3, g["wav"])
     print(f"\nh3 + h3 pairs: vs x6 {s36:.1f} dB, vs reference {s3r:.1f} dB")
     assert s36 >= 100 and s3r >= 80
+
+
+# ---- the wide stages' ParallelBlocks at edge lengths --------------------------------------------
+# The grouped launches (conv_gemm_x3dw_group / x3dq_group: the three ResBlocks' convs of one index in
+# one grid) are reachable through modules only.  A ParallelBlock runs five grouped launches and its
+# last three convs one by one (the mean folded into their epilogues fixes their order), on the single
+# launch of the same tiling.  Lengths: one and two rows, one row below the longest
+# tap span (k 11, dilation 5: 50 rows), one row either side of the tile heights (256; 384 at C = 128).
+X3DW_GROUP = "conv_gemm_x3dw_group<256,256,halo>"
+X3DW384_GROUP = "conv_gemm_x3dw_group<384,128,halo>"
+X3DQ128_GROUP = "conv_gemm_x3dq_group<256,128,halo>"
+X3DQ256_GROUP = "conv_gemm_x3dq_group<128,256,halo>"
+STAGE_GROUP = {0: X3DW_GROUP, 1: X3DW_GROUP, 2: X3DW384_GROUP}
+EDGE_CASES = [(st, L) for st in (0, 1, 2) for L in (1, 2, 49, 255, 257)] + [(2, 385)]
+
+
+def _module_kernels(eng, name, x):
+    """(output, names of the conv kernels the module launched)."""
+    eng.profile(True)
+    try:
+        eng.profile_reset()
+        y = eng.module(name, x)
+        prof = eng.profile_read()
+    finally:
+        eng.profile(False)
+        eng.profile_reset()
+    return y, {k for k, v in prof.items() if v["launches"] > 0 and k.startswith("conv_gemm")}
+
+
+def _group_and_single(group):
+    return {group, group.replace("_group", "")}
+
+
+@pytest.mark.parametrize("stage,L", EDGE_CASES)
+def test_wide_stage_edge_lengths(eng, state, cfg, stage, L):
+    """generator.resblocks.{0,1,2} on two different clips: the fp64 oracle under the 2e-4 contract (per
+    clip), the expected grouped kernel, the same bits under DCX_H3_BN = 128 / 256 and DCX_H3_SPLIT = 0,
+    and each clip alone the bits it has in the batch."""
+    from oracle import reference_cpu as R
+
+    name = f"generator.resblocks.{stage}"
+    C = cfg["decoder"]["upsample_initial_channel"] >> (stage + 1)
+    x = torch.from_numpy(np.random.default_rng(1000 * stage + L).standard_normal((2, C, L)).astype(np.float32))
+    ref = torch.nn.functional.silu(R.parallel_block(x.double(), state["generator"], stage, cfg["decoder"], torch.float64))
+    ref = ref.numpy()
+    xd = _cl(x.numpy())
+    y, names = _module_kernels(eng, name, xd)
+    assert names == _group_and_single(STAGE_GROUP[stage]), names
+    yn = y.cpu().numpy().transpose(0, 2, 1)
+    errs = [_rel(yn[c], ref[c]) for c in range(2)]
+    print(f"\nstage {stage} (C = {C}) L = {L}: h3 rel err per clip {errs[0]:.3g} {errs[1]:.3g}", end="")
+    assert max(errs) < 2e-4, errs
+    wide = {128: X3DQ128_GROUP, 256: X3DQ256_GROUP if C % 256 == 0 else STAGE_GROUP[stage]}
+    for knobs, kern in (({"DCX_H3_BN": 128}, wide[128]), ({"DCX_H3_BN": 256}, wide[256]),
+                        ({"DCX_H3_SPLIT": 0}, STAGE_GROUP[stage])):
+        with eng.knobs(**knobs):
+            y2, names = _module_kernels(eng, name, xd)
+        assert names == _group_and_single(kern), (knobs, names)
+        assert torch.equal(y2, y), knobs
+    for c in range(2):
+        assert torch.equal(eng.module(name, xd[c:c + 1].contiguous())[0], y[c]), f"clip {c} alone differs from the batch"
