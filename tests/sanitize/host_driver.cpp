@@ -2,8 +2,8 @@
 // runtime: the C ABI's argument checks, checkpoint ingestion (name / shape validation, weight-norm
 // folding, packing), workspace planning over many shapes and modes, and the MP3 decoder on its
 // demo input, every prefix of it and thousands of corrupted copies.  Built by `make -C
-// distilcodec_nabeel_amd/csrc sanitize` (dcx_api.cpp and dcx_mp3.cpp instrumented on the host,
-// the kernels linked as built); run by tests/test_sanitize.py.  Without a GPU, dcx_finalize fails
+// distilcodec_nabeel_amd/csrc sanitize` (every host unit of the Makefile's HOST list and dcx_mp3.cpp
+// instrumented on the host, the kernels linked as built); run by tests/test_sanitize.py.  Without a GPU, dcx_finalize fails
 // at its first device allocation (after the dry validation pass) and the stage calls are only
 // checked for their argument errors; with one, a small encode_decode runs too.
 //

@@ -1,7 +1,8 @@
 """Host runtime under AddressSanitizer + UndefinedBehaviorSanitizer (sanitizer runs of
 the host code on the CPU build).  `make -C distilcodec_nabeel_amd/csrc sanitize` builds
-tests/sanitize/host_driver.cpp against dcx_api.cpp and dcx_mp3.cpp instrumented on the host (the
-kernels as built).  The driver exercises the C ABI's argument checks, checkpoint ingestion (name and
+tests/sanitize/host_driver.cpp against the host units (csrc/Makefile's HOST list: dcx_weights,
+dcx_dispatch, dcx_stages, dcx_generator, dcx_module, dcx_api) and dcx_mp3.cpp instrumented on the
+host (the kernels as built).  The driver exercises the C ABI's argument checks, checkpoint ingestion (name and
 shape validation, weight packing up to the first device allocation), workspace planning for 35
 shapes x 3 arithmetic modes x split-K on/off, the conv primitive's checks, and the MP3 decoder on
 the reference's test.mp3, its prefixes, 400 corrupted copies and random garbage.  Any sanitizer
