@@ -47,8 +47,7 @@ static const struct {
   int dcx::Knobs::*slot;
 } kKnobs[] = {
     {"DCX_RP_R", &dcx::Knobs::rp_rows},                   {"DCX_RP_OLD", &dcx::Knobs::rp_old},
-    {"DCX_RP_G64", &dcx::Knobs::rp_g64},                  {"DCX_RP_SYNC", &dcx::Knobs::rp_sync},
-    {"DCX_RP_W4", &dcx::Knobs::rp_w4},                    {"DCX_GELU_LUT", &dcx::Knobs::gelu_lut},
+    {"DCX_RP_G64", &dcx::Knobs::rp_g64},                  {"DCX_GELU_LUT", &dcx::Knobs::gelu_lut},
     {"DCX_BF16_PERSIST", &dcx::Knobs::bf16_persist},      {"DCX_BF16_REG_EPI", &dcx::Knobs::bf16_reg_epi},
     {"DCX_DWCONV_TILED", &dcx::Knobs::dwconv_tiled},      {"DCX_SPLIT_MIN_STEPS", &dcx::Knobs::split_min_steps},
     {"DCX_SPLIT_GROUP_OFF", &dcx::Knobs::split_group_off}, {"DCX_H3", &dcx::Knobs::h3},

@@ -118,8 +118,6 @@ struct Knobs {
   int rp_rows = 0;          // DCX_RP_R: pair-kernel tile height (an instantiated size; 0 = the launcher's choice)
   int rp_old = 0;           // DCX_RP_OLD=1: the step-schedule pair kernel (conv_res_pair) at C = 32 too
   int rp_g64 = 0;           // DCX_RP_G64=1: the barrier-free 8-wave pair kernel at C = 64
-  int rp_sync = 0;          // DCX_RP_SYNC=n: a barrier after every n-th tap of conv_res_pair_g
-  int rp_w4 = 0;            // DCX_RP_W4=1: conv_res_pair_w4 (4-wave workgroups, two per CU; A/B)
   int gelu_lut = -1;        // DCX_GELU_LUT: conv_gemm_bf16dp's table limit (-1 = the whole table, 0 = evaluated)
   int bf16_persist = 1;     // DCX_BF16_PERSIST=0: the staged bf16dm for pwconv1 instead of bf16dp
   int bf16_reg_epi = 1;     // DCX_BF16_REG_EPI=0: the LDS-staged epilogue for pwconv1 too
@@ -262,10 +260,6 @@ struct ResPairParams {
   float* mean_out;
   long long bstride;  // elements between clips
   int L, batch, C;
-  // conv_res_pair_g: a workgroup barrier after every tap_sync-th tap of a conv (0: none), which
-  // bounds how far the two waves of a SIMD drift apart before the image hand-offs (set by
-  // launch_res_pair from kn)
-  int tap_sync;
   // h3 (conv_res_pair_h3): w1 / w2 are the ConvParams::w3 weights, scaled by 2^w3_shift{1,2}[m]
   int h3;
   int w3_shift1[kMaxGroup], w3_shift2[kMaxGroup];

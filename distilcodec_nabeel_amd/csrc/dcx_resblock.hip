@@ -30,120 +30,44 @@
 // is conflict-free at any tap offset, and a tap's row offset is one add per read set (round 5; the
 // round-2 layout of 16-row blocks cost ~6 VALU per row block and tap in address arithmetic).  The
 // weight slot is the global tap slice [chunk][Cout][96 B] copied as is.
+// The phases every pair kernel shares (geometry, the x6 / h3 arithmetics, S / T image, MFMA block,
+// weight fragments, tile loop, epilogue, stamps) are in dcx_resblock_common.h; here are the three
+// schedules and the launcher.
 #include <algorithm>
 #include <cstdio>
 
-#include "dcx_kernels.h"
-#include "dcx_planes.h"
+#include "dcx_resblock_common.h"
 
 namespace dcx {
-namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float rp_silu(float v) { return v * __builtin_amdgcn_rcpf(1.0f + __expf(-v)); }
-// barrier that leaves global loads in flight (only LDS traffic is drained)
-__device__ __forceinline__ void rp_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-typedef __attribute__((address_space(3))) void* rp_lds_t;
-// retire this wave's weight pieces: all but the n youngest vector-memory ops (the prefetch loads
-// issued after the pieces) done
-__device__ __forceinline__ void rp_wait(int n) {
-#define RP_W(k) \
-  case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-  switch (n) {
-    RP_W(1) RP_W(2) RP_W(3) RP_W(4) RP_W(5) RP_W(6) RP_W(7) RP_W(8) RP_W(9) RP_W(10) RP_W(11) RP_W(12)
-    RP_W(13) RP_W(14) RP_W(15) RP_W(16) RP_W(17) RP_W(18) RP_W(19) RP_W(20) RP_W(21) RP_W(22) RP_W(23) RP_W(24)
-    RP_W(25) RP_W(26) RP_W(27) RP_W(28) RP_W(29) RP_W(30) RP_W(31) RP_W(32)
-    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // n > 32 waits for more: always safe
-  }
-#undef RP_W
-}
-
-#ifdef RP_DIAG_STAMPS
-// Diagnostic build only: shader-clock sums per phase of conv_res_pair (wave 0 of every workgroup):
-// [0] c1 steps, [1] T image, [2] c2 steps, [3] epilogue, [4] next S image, [5] member-tiles,
-// [6] c1 steps counted, [7] c2 steps counted, [8] c1 step MFMA phases, [9] c1 step barrier waits.
-__device__ unsigned long long g_rp_diag[32];  // [C == 64][16]
-#define RP_T(v) const unsigned long long v = __builtin_amdgcn_s_memtime()
-#else
-#define RP_T(v)
-#endif
 
 // output rows per tile: 496 / 176 (C = 32 / 64) by default; the launcher takes fewer rows per tile
 // when a launch has too few tiles for the CUs (small batches: the C5 streaming hop), same bits
 template <int C>
 constexpr int kRpRows = C == 32 ? 496 : 176;
-template <int C, int RR = kRpRows<C>>
-struct RpGeom {
-  static constexpr int R = RR;
-  static constexpr int M1 = R + 16;              // c1 rows: [r0 - 8, r0 + R + 8)
-  static constexpr int H1 = 32;                  // largest c1 reach (k - 1) / 2 * d
-  static constexpr int NS = M1 + 2 * H1;         // S image rows
-  static constexpr int NCH = C / 16;             // K16 chunks per tap
-  static constexpr int WC = C / 32, WR = 8 / WC; // waves: WR row groups x WC column halves (32 ch)
-  static constexpr int NB1 = M1 / 16, RB1 = NB1 / WR;
-  static constexpr int NB2 = R / 16, RB2 = (NB2 + WR - 1) / WR;
-  static constexpr int PS = NS * 16;             // bytes per piece of one chunk (image layout below)
-  static constexpr int IMG = NCH * 6 * PS;       // S image bytes (T reuses its start)
-  static constexpr int TPS = C == 32 ? 2 : 1;    // taps per step (weight slot)
-  static constexpr int WTAP = C * C * 6;         // one tap of weights
-  static constexpr int WSLOT = TPS * WTAP;
-  static constexpr int G8 = C / 8;               // 8-channel groups per row
-  static constexpr int NIT = (NS * G8 + 511) / 512;
-  static constexpr int WP = WSLOT / 1024, WPW = (WP + 7) / 8;  // DMA pieces per slot, per wave
-  static constexpr int LDS = IMG + 2 * WSLOT + 2 * kMaxGroup * C * 4;
-  static_assert(NB1 % WR == 0 && RB1 == RB2, "row blocks per wave");
-  static_assert(WSLOT % 1024 == 0 && LDS <= 160 * 1024, "LDS");
-};
-
-// conv_res_pair_h3's geometry: RpGeom's rows and wave layout, h3 images (8 pieces of 16 B per row
-// and 32-channel chunk: 4 B per element), so taller tiles fit the LDS
+// conv_res_pair_h3: h3 images are 4 B per element instead of 6, so taller tiles fit the LDS
 template <int C>
 constexpr int kRp3Rows = C == 32 ? 624 : 240;
-template <int C, int RR = kRp3Rows<C>>
-struct RpGeom3 {
-  static constexpr int R = RR;
-  static constexpr int M1 = R + 16, H1 = 32, NS = M1 + 2 * H1;
-  static constexpr int WC = C / 32, WR = 8 / WC;
-  static constexpr int NB1 = M1 / 16, RB1 = NB1 / WR;
-  static constexpr int NB2 = R / 16, RB2 = (NB2 + WR - 1) / WR;
-  static constexpr int PS = NS * 16;
-  static constexpr int NCH = C / 32;            // K32 chunks per tap
-  static constexpr int IMG = NCH * 8 * PS;      // S image bytes (T reuses it)
-  static constexpr int WTAP = C * C * 4;        // one tap of h3 weights (bytes)
-  static constexpr int G8 = C / 8;
-  static constexpr int NIT = (NS * G8 + 511) / 512;
-  static_assert(NB1 % WR == 0 && RB1 == RB2, "row blocks per wave");
-  static_assert(IMG + 2 * kMaxGroup * C * 4 <= 160 * 1024, "LDS");
-};
-
-}  // namespace
 
 template <int C, bool MEAN, int RR = kRpRows<C>>
 __global__ void __launch_bounds__(512, 1) conv_res_pair(const ResPairParams p) {
-  using G = RpGeom<C, RR>;
-  constexpr int R = G::R, NCH = G::NCH, WR = G::WR, RB = G::RB1, PS = G::PS, IMG = G::IMG, TPS = G::TPS;
-  constexpr int WTAP = G::WTAP, WSLOT = G::WSLOT, G8 = G::G8, NIT = G::NIT, WP = G::WP, WPW = G::WPW, NS = G::NS;
-  __shared__ __attribute__((aligned(16))) char lds[G::LDS];
+  using A = RpX6;
+  using G = RpGeom<A, C, RR>;
+  constexpr int NCH = G::NCH, WR = G::WR, RB = G::RB1, PS = G::PS, IMG = G::IMG, WTAP = G::WTAP, NIT = G::NIT;
+  constexpr int TPS = C == 32 ? 2 : 1;  // taps per step (weight slot)
+  constexpr int WSLOT = TPS * WTAP;
+  constexpr int WP = WSLOT / 1024, WPW = (WP + 7) / 8;  // DMA pieces per slot, per wave
+  constexpr int LDS = IMG + 2 * WSLOT + G::BIASB;
+  static_assert(WSLOT % 1024 == 0 && LDS <= 160 * 1024, "LDS");
+  __shared__ __attribute__((aligned(16))) char lds[LDS];
   float* const bias_lds = reinterpret_cast<float*>(lds + IMG + 2 * WSLOT);  // [conv][member][C]
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wc = wave % G::WC, wr = wave / G::WC;
-  const int l15 = lane & 15, hf = (lane >> 4) & 1, t = lane >> 5;
+  const RpLane ln = RpLane::make<G>();
+  const int tid = ln.tid, lane = ln.lane, wave = ln.wave, wr = ln.wr;
   const int L = p.L, nmem = p.nmem;
-  const int ntl = (L + R - 1) / R;
-  const int total = ntl * p.batch;
 
   // ---- weight ring: LDS-DMA of a step's taps (lane-linear 1 KiB pieces, no staging registers);
   // taps past the conv's last read zeros (outside the buffer descriptor) and are never used ----
   auto issue_w = [&](int m, int conv, int step, int slot) {
-#ifdef RP_DIAG_NODMA  // timing build: weights never refilled after the prologue (wrong results)
-    if (step > 0 || conv > 0 || m > 0) return;
-#endif
     const int k = p.taps[m], j0 = step * TPS;
     const unsigned short* w = (conv ? p.w2[m] : p.w1[m]) + (long long)j0 * (WTAP / 2);
     const __amdgpu_buffer_rsrc_t rw =
@@ -158,49 +82,13 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair(const ResPairParams p) {
     asm volatile("" ::: "memory");  // later loads stay younger than the pieces (rp_wait counts them)
   };
 
-  // ---- S image fill: state rows -> registers (issue) -> silu, planes, LDS (commit) ----
-  f32x4 pf[NIT][2];
-  auto issue_fill_item = [&](const float* src, int r0, int k) {
-    const int it = min(tid + 512 * k, NS * G8 - 1);  // unconditional (rp_wait counts the loads)
-    const int s = ((it >> 3) / G8) * 8 + (it & 7), g8 = (it >> 3) % G8;
-    const int a = min(max(r0 - 8 - G::H1 + s, 0), L - 1);
-    const f32x4* q = reinterpret_cast<const f32x4*>(src + (long long)a * C + g8 * 8);
-    pf[k][0] = q[0];
-    pf[k][1] = q[1];
-  };
-  auto commit_fill = [&](int r0) {
-#pragma unroll
-    for (int k = 0; k < NIT; ++k) {
-      const int it = tid + 512 * k;
-      if (!(NIT * 512 == NS * G8 || it < NS * G8)) continue;
-      const int s = ((it >> 3) / G8) * 8 + (it & 7), g8 = (it >> 3) % G8;
-      const int a = r0 - 8 - G::H1 + s;
-      const bool ok = a >= 0 && a < L;
-      s16x8 hv, mv, lv;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float sv = rp_silu(pf[k][e >> 2][e & 3]);
-        const float v = ok ? sv : 0.f;
-        unsigned short h, m, l;
-        split3(v, h, m, l);
-        hv[e] = (short)h;
-        mv[e] = (short)m;
-        lv[e] = (short)l;
-      }
-      char* d = lds + ((g8 >> 1) * 6 + (g8 & 1) * 3) * PS + s * 16;
-      *reinterpret_cast<s16x8*>(d) = hv;
-      *reinterpret_cast<s16x8*>(d + PS) = mv;
-      *reinterpret_cast<s16x8*>(d + 2 * PS) = lv;
-    }
-  };
+  f32x4 pf[NIT][2];  // the next S image's rows in flight
 
   // ---- one step: the step's taps, every chunk, rows of this wave, its 2 column blocks.  hook(i)
   // runs after row block i of the first tap (global loads spread between the MFMAs) ----
-  // lane parts of the three activation reads (piece, row within the 16-row block); a tap adds its
-  // wave-uniform row offset once, and row block / chunk offsets are instruction immediates
-  const int pk0 = ((hf * 3 + t) * NS + l15) * 16, pk1 = ((hf * 3 + (t ? 0 : 1)) * NS + l15) * 16;
-  const int pk2 = ((hf * 3 + (t ? 0 : 2)) * NS + l15) * 16;
-  auto mfma_step = [&](f32x4 (&acc)[RB][2], int slot, int ntaps, int row0, int rstep, int nrb, auto hook) {
+  const A::Wo wo = A::wo(lane, ln.wc);
+  const A::Xb xl = A::xlane<G::NS>(lds, lane);
+  auto mfma_step = [&](RpRow (&acc)[RB], int slot, int ntaps, int row0, int rstep, int nrb, auto hook) {
 #pragma unroll
     for (int u = 0; u < TPS; ++u) {
       if (u >= ntaps) break;
@@ -210,33 +98,17 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair(const ResPairParams p) {
       for (int ch = 0; ch < NCH; ++ch)
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) {
-          const char* w = wb + (ch * C + (2 * wc + cb) * 16 + l15) * 96 + hf * 48;
-          wf[ch][cb][0] = *reinterpret_cast<const s16x8*>(w + t * 16);        // {h', m'}
-          wf[ch][cb][1] = *reinterpret_cast<const s16x8*>(w + (t ? 32 : 0));  // {h', l'}
+          const char* w = wb + (ch * C + cb * 16) * G::WROW;
+          wf[ch][cb][0] = *reinterpret_cast<const s16x8*>(w + wo.o0);  // {h', m'}
+          wf[ch][cb][1] = *reinterpret_cast<const s16x8*>(w + wo.o1);  // {h', l'}
         }
-      const int rowoff = row0 + u * rstep;
-      const int tb = (wr * 16 + rowoff) * 16;
-      const char *xb0 = lds + pk0 + tb, *xb1 = lds + pk1 + tb, *xb2 = lds + pk2 + tb;
+      const A::Xb x = A::at(xl, (wr * 16 + row0 + u * rstep) * 16);
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
       for (int i = 0; i < RB; ++i) {
         if (i < nrb) {
-          const int io = (WR * 16 * i) * 16;
 #pragma unroll
-          for (int ch = 0; ch < NCH; ++ch) {
-            const s16x8 x2 = *reinterpret_cast<const s16x8*>(xb2 + io + ch * 6 * PS);
-            const s16x8 x1 = *reinterpret_cast<const s16x8*>(xb1 + io + ch * 6 * PS);
-            const s16x8 x0 = *reinterpret_cast<const s16x8*>(xb0 + io + ch * 6 * PS);
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb) {
-              acc[i][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[ch][cb][1]),
-                                                                   __builtin_bit_cast(bf16x8, x2), acc[i][cb], 0, 0, 0);
-              acc[i][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[ch][cb][0]),
-                                                                   __builtin_bit_cast(bf16x8, x1), acc[i][cb], 0, 0, 0);
-              acc[i][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[ch][cb][0]),
-                                                                   __builtin_bit_cast(bf16x8, x0), acc[i][cb], 0, 0, 0);
-            }
-          }
+          for (int ch = 0; ch < NCH; ++ch) rp_block<A>(acc[i], wf[ch], x, (WR * 16 * i) * 16 + ch * A::PPC * PS);
         }
         if (u == 0) hook(i);
       }
@@ -247,86 +119,51 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair(const ResPairParams p) {
 
   // rows of c2 this wave owns
   const int nrb2 = min(RB, (G::NB2 - wr + WR - 1) / WR);
-  int tile = blockIdx.x;
-  if (tile >= total) return;  // whole workgroup, before any barrier
-  int b = tile / ntl, r0 = (tile - b * ntl) * R;
+  RpTiles<G::R> tl;
+  if (!tl.first(p)) return;  // whole workgroup, before any barrier
   // prologue: biases, first ResBlock's S image and first weight step
-  if (tid < 2 * nmem * C) {
-    const int conv = tid / (nmem * C), m = (tid / C) % nmem, c = tid % C;
-    bias_lds[(conv * kMaxGroup + m) * C + c] = (conv ? p.b2[m] : p.b1[m])[c];
-  }
+  rp_bias_prologue<C>(bias_lds, p, tid);
   issue_w(0, 0, 0, 0);
 #pragma unroll
-  for (int k = 0; k < NIT; ++k) issue_fill_item(p.src[0] + (long long)b * p.bstride, r0, k);
-  commit_fill(r0);
+  for (int k = 0; k < NIT; ++k) rp_fill_issue<G, C>(pf[k], p.src[0] + (long long)tl.b * p.bstride, tl.r0, L, tid, k);
+  rp_fill_commit<A, G>(lds, pf, tl.r0, L, tid);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   rp_barrier();
   int slot = 0;
-  f32x4 macc[MEAN ? RB : 1][2];
-#ifdef RP_DIAG_STAMPS
-  unsigned long long dg[16] = {};
-#endif
+  RpRow macc[MEAN ? RB : 1];
+  RP_STAMP(RpStamps st;)
   for (;;) {
-    const int next_tile = tile + gridDim.x;
-    const bool more = next_tile < total;
-    const int nb = more ? next_tile / ntl : 0, nr0 = more ? (next_tile - nb * ntl) * R : 0;
+    tl.look_ahead();
+    const int r0 = tl.r0;
     for (int m = 0; m < nmem; ++m) {
       const int k = p.taps[m], hk = (k - 1) >> 1, d = p.dil[m];
       const int nst = (k + TPS - 1) / TPS;  // steps per conv
-      const long long cb0 = (long long)b * p.bstride;
+      const long long cb0 = (long long)tl.b * p.bstride;
       const bool last_m = m + 1 == nmem;
-      const bool has_next = !last_m || more;
-      f32x4 acc[RB][2];
+      const bool has_next = !last_m || tl.more;
+      RpRow acc[RB];
       RP_T(ta);
       // ---- c1 over rows [r0 - 8, r0 + R + 8) from the S image
 #pragma unroll
-      for (int i = 0; i < RB; ++i) acc[i][0] = acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+      for (int i = 0; i < RB; ++i) acc[i].zero();
       for (int j = 0; j < nst; ++j) {
         if (j + 1 < nst) issue_w(m, 0, j + 1, slot ^ 1);
         else issue_w(m, 1, 0, slot ^ 1);
         RP_T(s1);
         mfma_step(acc, slot, min(TPS, k - j * TPS), G::H1 + (j * TPS - hk) * d, d, RB, no_hook);
         RP_T(s2);
-#ifndef RP_DIAG_NOWAIT  // timing build: the next slot's pieces are not waited for (wrong results)
         rp_wait(0);
-#endif
         rp_barrier();
-#ifdef RP_DIAG_STAMPS
-        {
+        RP_STAMP({
           RP_T(s3);
-          dg[8] += s2 - s1;
-          dg[9] += s3 - s2;
-        }
-#endif
+          st.dg[8] += s2 - s1;
+          st.dg[9] += s3 - s2;
+        })
         slot ^= 1;
       }
       RP_T(tb);
       // ---- T image: silu(c1 + b1) planes over the S image (zero outside the clip)
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb) {
-        const int c0 = (2 * wc + cb) * 16 + 4 * (lane >> 4);
-        const f32x4 bias = *reinterpret_cast<const f32x4*>(bias_lds + m * C + c0);
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-          const int ir = (wr + WR * i) * 16 + l15, a = r0 - 8 + ir;
-          const bool ok = a >= 0 && a < L;
-          s16x4 hv, mv, lv;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float sv = rp_silu(acc[i][cb][e] + bias[e]);
-            const float v = ok ? sv : 0.f;
-            unsigned short h, mm, l;
-            split3(v, h, mm, l);
-            hv[e] = (short)h;
-            mv[e] = (short)mm;
-            lv[e] = (short)l;
-          }
-          char* dst = lds + ((c0 >> 4) * 6 + ((c0 >> 3) & 1) * 3) * PS + ir * 16 + (c0 & 7) * 2;
-          *reinterpret_cast<s16x4*>(dst) = hv;
-          *reinterpret_cast<s16x4*>(dst + PS) = mv;
-          *reinterpret_cast<s16x4*>(dst + 2 * PS) = lv;
-        }
-      }
+      rp_t_image<A, G, C>(lds, bias_lds + m * C, acc, ln, r0, L);
       rp_barrier();
       RP_T(tc);
       // ---- c2 over rows [r0, r0 + R) from the T image.  Step 0 loads the residual rows, step 1 (or
@@ -334,23 +171,16 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair(const ResPairParams p) {
       // block's share between the MFMAs of each, after the step's weight pieces.  The two steps are
       // peeled out of the loop: a load pending across the loop's back edge made hipcc wait for it.
 #pragma unroll
-      for (int i = 0; i < RB; ++i) acc[i][0] = acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      const float* nsrc = !last_m ? p.src[m + 1] + cb0 : p.src[0] + (long long)nb * p.bstride;
-      const int nsr0 = !last_m ? r0 : nr0;
+      for (int i = 0; i < RB; ++i) acc[i].zero();
+      const float* nsrc = !last_m ? p.src[m + 1] + cb0 : p.src[0] + (long long)tl.nb * p.bstride;
+      const int nsr0 = !last_m ? r0 : tl.nr0;
       const int jpf = nst > 1 ? 1 : 0;
-      f32x4 res[RB][2];
-      auto res_hook = [&](int i) {
-        const int q = min(r0 + (wr + WR * i) * 16 + l15, L - 1);
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-          const int c0 = (2 * wc + cb) * 16 + 4 * (lane >> 4);
-          res[i][cb] = *reinterpret_cast<const f32x4*>(p.src[m] + cb0 + (long long)q * C + c0);
-        }
-      };
+      RpRow res[RB];
+      auto res_hook = [&](int i) { rp_load_res<G, C>(res[i], p.src[m] + cb0, ln, r0, L, i); };
       auto pf_hook = [&](int i) {
         if (!has_next) return;
 #pragma unroll
-        for (int kk = NIT * i / RB; kk < NIT * (i + 1) / RB; ++kk) issue_fill_item(nsrc, nsr0, kk);
+        for (int kk = NIT * i / RB; kk < NIT * (i + 1) / RB; ++kk) rp_fill_issue<G, C>(pf[kk], nsrc, nsr0, L, tid, kk);
       };
       auto both_hook = [&](int i) {
         res_hook(i);
@@ -379,60 +209,27 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair(const ResPairParams p) {
       for (int j = jpf + 1; j < nst; ++j) {
         c2_issue_w(j);
         mfma_step(acc, slot, min(TPS, k - j * TPS), 8 + j * TPS - hk, 1, nrb2, no_hook);
-#ifndef RP_DIAG_NOWAIT
         rp_wait(0);
-#endif
         rp_barrier();
         slot ^= 1;
       }
       RP_T(te);
       // ---- epilogue: state + c2 + b2 (rows past the clip end are dropped)
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb) {
-        const int c0 = (2 * wc + cb) * 16 + 4 * (lane >> 4);
-        const f32x4 bias = *reinterpret_cast<const f32x4*>(bias_lds + (kMaxGroup + m) * C + c0);
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-          if (i >= nrb2) break;
-          const int q = r0 + (wr + WR * i) * 16 + l15;
-          const f32x4 v = res[i][cb] + (acc[i][cb] + bias);
-          if constexpr (!MEAN) {
-            if (q < L) *reinterpret_cast<f32x4*>(p.dst[m] + cb0 + (long long)q * C + c0) = v;
-          } else if (m == 0) {
-            macc[i][cb] = v;
-          } else if (!last_m) {
-            macc[i][cb] = macc[i][cb] + v;
-          } else {
-            const f32x4 mv = (macc[i][cb] + v) / 3.0f;
-            f32x4 sv;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sv[e] = rp_silu(mv[e]);
-            if (q < L) *reinterpret_cast<f32x4*>(p.mean_out + cb0 + (long long)q * C + c0) = sv;
-          }
-        }
-      }
+      rp_epilogue<A, G, C, MEAN>(p, bias_lds + (kMaxGroup + m) * C, acc, res, macc, ln, m, cb0, r0, nrb2);
       RP_T(tf);
       if (has_next) {
-        commit_fill(nsr0);
+        rp_fill_commit<A, G>(lds, pf, nsr0, L, tid);
         rp_barrier();
       }
-#ifdef RP_DIAG_STAMPS
-      {
+      RP_STAMP({
         RP_T(tg);
-        dg[0] += tb - ta; dg[1] += tc - tb; dg[2] += te - tc; dg[3] += tf - te; dg[4] += tg - tf;
-        dg[5] += 1; dg[6] += nst; dg[7] += nst;
-      }
-#endif
+        st.member(ta, tb, tc, te, tf, tg, nst);
+      })
     }
-    if (!more) break;
-    tile = next_tile;
-    b = nb;
-    r0 = nr0;
+    if (!tl.more) break;
+    tl.advance();
   }
-#ifdef RP_DIAG_STAMPS
-  if (tid == 0)
-    for (int i = 0; i < 16; ++i) atomicAdd(&g_rp_diag[(C == 64 ? 16 : 0) + i], dg[i]);
-#endif
+  RP_STAMP(st.flush(C, tid);)
 }
 
 // Barrier-free tap loops (round 3): conv_res_pair_g.  conv_res_pair's per-step stamps put a c1 tap
@@ -448,110 +245,34 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair(const ResPairParams p) {
 // layouts are conv_res_pair's, so the results are the same bits.
 template <int C, bool MEAN, int RR = kRpRows<C>>
 __global__ void __launch_bounds__(512, 1) conv_res_pair_g(const ResPairParams p) {
-  using G = RpGeom<C, RR>;
-  constexpr int R = G::R, NCH = G::NCH, WR = G::WR, RB = G::RB1, PS = G::PS, IMG = G::IMG;
-  constexpr int G8 = G::G8, NIT = G::NIT, NS = G::NS, WTAP = G::WTAP;
-  __shared__ __attribute__((aligned(16))) char lds[IMG + 2 * kMaxGroup * C * 4];
+  using A = RpX6;
+  using G = RpGeom<A, C, RR>;
+  constexpr int NCH = G::NCH, WR = G::WR, RB = G::RB1, PS = G::PS, IMG = G::IMG, NIT = G::NIT;
+  __shared__ __attribute__((aligned(16))) char lds[IMG + G::BIASB];
   float* const bias_lds = reinterpret_cast<float*>(lds + IMG);  // [conv][member][C]
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wc = wave % G::WC, wr = wave / G::WC;
-  const int l15 = lane & 15, hf = (lane >> 4) & 1, t = lane >> 5;
+  const RpLane ln = RpLane::make<G>();
+  const int tid = ln.tid, lane = ln.lane, wr = ln.wr;
   const int L = p.L, nmem = p.nmem;
-  const int ntl = (L + R - 1) / R;
-  const int total = ntl * p.batch;
 
-  // ---- S image fill (as conv_res_pair) ----
-  f32x4 pf[NIT][2];
-  auto issue_fill_item = [&](const float* src, int r0, int k) {
-    const int it = min(tid + 512 * k, NS * G8 - 1);
-    const int s = ((it >> 3) / G8) * 8 + (it & 7), g8 = (it >> 3) % G8;
-    const int a = min(max(r0 - 8 - G::H1 + s, 0), L - 1);
-    const f32x4* q = reinterpret_cast<const f32x4*>(src + (long long)a * C + g8 * 8);
-    pf[k][0] = q[0];
-    pf[k][1] = q[1];
-  };
-  auto commit_fill = [&](int r0) {
-#pragma unroll
-    for (int k = 0; k < NIT; ++k) {
-      const int it = tid + 512 * k;
-      if (!(NIT * 512 == NS * G8 || it < NS * G8)) continue;
-      const int s = ((it >> 3) / G8) * 8 + (it & 7), g8 = (it >> 3) % G8;
-      const int a = r0 - 8 - G::H1 + s;
-      const bool ok = a >= 0 && a < L;
-      s16x8 hv, mv, lv;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float sv = rp_silu(pf[k][e >> 2][e & 3]);
-        const float v = ok ? sv : 0.f;
-        unsigned short h, m, l;
-        split3(v, h, m, l);
-        hv[e] = (short)h;
-        mv[e] = (short)m;
-        lv[e] = (short)l;
-      }
-      char* d = lds + ((g8 >> 1) * 6 + (g8 & 1) * 3) * PS + s * 16;
-      *reinterpret_cast<s16x8*>(d) = hv;
-      *reinterpret_cast<s16x8*>(d + PS) = mv;
-      *reinterpret_cast<s16x8*>(d + 2 * PS) = lv;
-    }
-  };
-
-  // ---- weight fragments of chunk ch of a tap ([chunk][Cout][96 B], the ConvParams::w6 tap slice):
-  // [column block][{h',m'} | {h',l'}] ----
-  s16x8 wf[NCH][2][2];
-  // buffer loads: the lane offsets are loop-invariant VGPRs, the tap base a scalar resource and the
-  // chunk / column-block offsets scalar constants, so a reload costs no address arithmetic
-  const int wo0 = ((2 * wc) * 16 + l15) * 96 + hf * 48 + t * 16, wo1 = ((2 * wc) * 16 + l15) * 96 + hf * 48 + (t ? 32 : 0);
-  auto load_wf = [&](const unsigned short* wtap, int ch) {
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)wtap, 0, WTAP, 0x00020000);
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb) {
-      const int so = (ch * C + cb * 16) * 96;
-      wf[ch][cb][0] = __builtin_bit_cast(s16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, wo0, so, 0));
-      wf[ch][cb][1] = __builtin_bit_cast(s16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, wo1, so, 0));
-    }
-  };
-  // the tap after tap j of conv `conv` of member m: the stream runs c1, c2 of each member, then
-  // member 0 again (the next tile; past the last tile harmless loads of weights already used)
-  auto next_tap = [&](int m, int conv, int j) -> const unsigned short* {
-    if (j + 1 < p.taps[m]) return (conv ? p.w2[m] : p.w1[m]) + (long long)(j + 1) * (WTAP / 2);
-    if (conv == 0) return p.w2[m];
-    return p.w1[m + 1 < nmem ? m + 1 : 0];
-  };
+  f32x4 pf[NIT][2];      // the next S image's rows in flight
+  s16x8 wf[NCH][2][2];  // the weight fragments of a tap, [chunk][column block][{h',m'} | {h',l'}]
+  const A::Wo wo = A::wo(lane, ln.wc);
+  const A::Xb xl = A::xlane<G::NS>(lds, lane);
 
   // ---- one tap, chunk-major: the MFMAs of chunk ch for every row block of the wave, then chunk ch
   // of the next tap into the fragment registers; hook() once every reload of the tap is issued (its
   // loads are then younger than the fragments the next tap waits for) ----
-  // lane parts of the three activation reads (piece, row within the 16-row block); a tap adds its
-  // wave-uniform row offset once, and row block / chunk offsets are instruction immediates
-  const int pk0 = ((hf * 3 + t) * NS + l15) * 16, pk1 = ((hf * 3 + (t ? 0 : 1)) * NS + l15) * 16;
-  const int pk2 = ((hf * 3 + (t ? 0 : 2)) * NS + l15) * 16;
-  auto tap = [&](f32x4 (&acc)[RB][2], int rowoff, int nrb, const unsigned short* wnext, auto hook) {
-    const int tb = (wr * 16 + rowoff) * 16;
-    const char *xb0 = lds + pk0 + tb, *xb1 = lds + pk1 + tb, *xb2 = lds + pk2 + tb;
+  auto tap = [&](RpRow (&acc)[RB], int rowoff, int nrb, const unsigned short* wnext, auto hook) {
+    const A::Xb x = A::at(xl, (wr * 16 + rowoff) * 16);
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch) {
 #pragma unroll
       for (int i = 0; i < RB; ++i) {
-        if (i < nrb) {
-          const int io = (WR * 16 * i) * 16 + ch * 6 * PS;
-          const s16x8 x2 = *reinterpret_cast<const s16x8*>(xb2 + io);
-          const s16x8 x1 = *reinterpret_cast<const s16x8*>(xb1 + io);
-          const s16x8 x0 = *reinterpret_cast<const s16x8*>(xb0 + io);
-#pragma unroll
-          for (int cb = 0; cb < 2; ++cb) {
-            acc[i][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[ch][cb][1]),
-                                                                 __builtin_bit_cast(bf16x8, x2), acc[i][cb], 0, 0, 0);
-            acc[i][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[ch][cb][0]),
-                                                                 __builtin_bit_cast(bf16x8, x1), acc[i][cb], 0, 0, 0);
-            acc[i][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[ch][cb][0]),
-                                                                 __builtin_bit_cast(bf16x8, x0), acc[i][cb], 0, 0, 0);
-          }
-        }
+        if (i < nrb) rp_block<A>(acc[i], wf[ch], x, (WR * 16 * i) * 16 + ch * A::PPC * PS);
       }
-      load_wf(wnext, ch);
+      rp_load_wf<A, G, C>(wf[ch], wnext, ch, wo);
       // keep the reloads here: left to itself the scheduler sinks all of them to the end of the tap,
       // and the next tap's first MFMAs then wait a whole L2 round trip
       __builtin_amdgcn_sched_barrier(0);
@@ -562,70 +283,35 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair_g(const ResPairParams p)
   auto no_hook = [] {};
 
   const int nrb2 = min(RB, (G::NB2 - wr + WR - 1) / WR);
-  int tile = blockIdx.x;
-  if (tile >= total) return;  // whole workgroup, before any barrier
-  int b = tile / ntl, r0 = (tile - b * ntl) * R;
-  if (tid < 2 * nmem * C) {
-    const int conv = tid / (nmem * C), m = (tid / C) % nmem, c = tid % C;
-    bias_lds[(conv * kMaxGroup + m) * C + c] = (conv ? p.b2[m] : p.b1[m])[c];
-  }
+  RpTiles<G::R> tl;
+  if (!tl.first(p)) return;  // whole workgroup, before any barrier
+  rp_bias_prologue<C>(bias_lds, p, tid);
 #pragma unroll
-  for (int ch = 0; ch < NCH; ++ch) load_wf(p.w1[0], ch);
+  for (int ch = 0; ch < NCH; ++ch) rp_load_wf<A, G, C>(wf[ch], p.w1[0], ch, wo);
 #pragma unroll
-  for (int k = 0; k < NIT; ++k) issue_fill_item(p.src[0] + (long long)b * p.bstride, r0, k);
-  commit_fill(r0);
+  for (int k = 0; k < NIT; ++k) rp_fill_issue<G, C>(pf[k], p.src[0] + (long long)tl.b * p.bstride, tl.r0, L, tid, k);
+  rp_fill_commit<A, G>(lds, pf, tl.r0, L, tid);
   rp_barrier();
-  f32x4 macc[MEAN ? RB : 1][2];
-#ifdef RP_DIAG_STAMPS
-  unsigned long long dg[16] = {};
-#endif
+  RpRow macc[MEAN ? RB : 1];
+  RP_STAMP(RpStamps st;)
   for (;;) {
-    const int next_tile = tile + gridDim.x;
-    const bool more = next_tile < total;
-    const int nb = more ? next_tile / ntl : 0, nr0 = more ? (next_tile - nb * ntl) * R : 0;
+    tl.look_ahead();
+    const int r0 = tl.r0;
     for (int m = 0; m < nmem; ++m) {
       const int k = p.taps[m], hk = (k - 1) >> 1, d = p.dil[m];
-      const long long cb0 = (long long)b * p.bstride;
+      const long long cb0 = (long long)tl.b * p.bstride;
       const bool last_m = m + 1 == nmem;
-      const bool has_next = !last_m || more;
-      f32x4 acc[RB][2];
+      const bool has_next = !last_m || tl.more;
+      RpRow acc[RB];
       RP_T(ta);
       // ---- c1 over rows [r0 - 8, r0 + R + 8) from the S image
 #pragma unroll
-      for (int i = 0; i < RB; ++i) acc[i][0] = acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      const int ts = p.tap_sync;
-      for (int j = 0; j < k; ++j) {
-        tap(acc, G::H1 + (j - hk) * d, RB, next_tap(m, 0, j), no_hook);
-        if (ts && (j + 1) % ts == 0 && j + 1 < k) rp_barrier();  // workgroup-uniform
-      }
+      for (int i = 0; i < RB; ++i) acc[i].zero();
+      for (int j = 0; j < k; ++j) tap(acc, G::H1 + (j - hk) * d, RB, rp_next_tap<G>(p, m, 0, j), no_hook);
       RP_T(tb);
       rp_barrier();  // every wave's S reads are done before T overwrites them
       // ---- T image: silu(c1 + b1) planes over the S image (zero outside the clip)
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb) {
-        const int c0 = (2 * wc + cb) * 16 + 4 * (lane >> 4);
-        const f32x4 bias = *reinterpret_cast<const f32x4*>(bias_lds + m * C + c0);
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-          const int ir = (wr + WR * i) * 16 + l15, a = r0 - 8 + ir;
-          const bool ok = a >= 0 && a < L;
-          s16x4 hv, mv, lv;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float sv = rp_silu(acc[i][cb][e] + bias[e]);
-            const float v = ok ? sv : 0.f;
-            unsigned short h, mm, l;
-            split3(v, h, mm, l);
-            hv[e] = (short)h;
-            mv[e] = (short)mm;
-            lv[e] = (short)l;
-          }
-          char* dst = lds + ((c0 >> 4) * 6 + ((c0 >> 3) & 1) * 3) * PS + ir * 16 + (c0 & 7) * 2;
-          *reinterpret_cast<s16x4*>(dst) = hv;
-          *reinterpret_cast<s16x4*>(dst + PS) = mv;
-          *reinterpret_cast<s16x4*>(dst + 2 * PS) = lv;
-        }
-      }
+      rp_t_image<A, G, C>(lds, bias_lds + m * C, acc, ln, r0, L);
       rp_barrier();
       RP_T(tc);
       // ---- c2 over rows [r0, r0 + R) from the T image.  Tap 0 loads the residual rows, taps 1 and 2
@@ -633,91 +319,43 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair_g(const ResPairParams p)
       // tap's fragment reloads (k >= 3, so taps 0..2 exist; they are peeled so that the register
       // arrays are indexed by constants)
 #pragma unroll
-      for (int i = 0; i < RB; ++i) acc[i][0] = acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      const float* nsrc = !last_m ? p.src[m + 1] + cb0 : p.src[0] + (long long)nb * p.bstride;
-      const int nsr0 = !last_m ? r0 : nr0;
-      f32x4 res[RB][2];
+      for (int i = 0; i < RB; ++i) acc[i].zero();
+      const float* nsrc = !last_m ? p.src[m + 1] + cb0 : p.src[0] + (long long)tl.nb * p.bstride;
+      const int nsr0 = !last_m ? r0 : tl.nr0;
+      RpRow res[RB];
       auto res_hook = [&] {
 #pragma unroll
-        for (int i = 0; i < RB; ++i) {
-          const int q = min(r0 + (wr + WR * i) * 16 + l15, L - 1);
-#pragma unroll
-          for (int cb = 0; cb < 2; ++cb) {
-            const int c0 = (2 * wc + cb) * 16 + 4 * (lane >> 4);
-            res[i][cb] = *reinterpret_cast<const f32x4*>(p.src[m] + cb0 + (long long)q * C + c0);
-          }
-        }
+        for (int i = 0; i < RB; ++i) rp_load_res<G, C>(res[i], p.src[m] + cb0, ln, r0, L, i);
       };
       auto pf_hook0 = [&] {
-        if (!has_next) return;
-#pragma unroll
-        for (int kk = 0; kk < NIT / 2; ++kk) issue_fill_item(nsrc, nsr0, kk);
+        if (has_next) rp_fill_issue_range<G, C, 0, NIT / 2>(pf, nsrc, nsr0, L, tid);
       };
       auto pf_hook1 = [&] {
-        if (!has_next) return;
-#pragma unroll
-        for (int kk = NIT / 2; kk < NIT; ++kk) issue_fill_item(nsrc, nsr0, kk);
+        if (has_next) rp_fill_issue_range<G, C, NIT / 2, NIT>(pf, nsrc, nsr0, L, tid);
       };
-      tap(acc, 8 - hk, nrb2, next_tap(m, 1, 0), res_hook);
-      if (ts == 1) rp_barrier();
-      tap(acc, 9 - hk, nrb2, next_tap(m, 1, 1), pf_hook0);
-      if (ts && 2 % ts == 0) rp_barrier();
-      tap(acc, 10 - hk, nrb2, next_tap(m, 1, 2), pf_hook1);
-      if (ts && 3 % ts == 0 && 3 < k) rp_barrier();
-      for (int j = 3; j < k; ++j) {
-        tap(acc, 8 + j - hk, nrb2, next_tap(m, 1, j), no_hook);
-        if (ts && (j + 1) % ts == 0 && j + 1 < k) rp_barrier();
-      }
+      tap(acc, 8 - hk, nrb2, rp_next_tap<G>(p, m, 1, 0), res_hook);
+      tap(acc, 9 - hk, nrb2, rp_next_tap<G>(p, m, 1, 1), pf_hook0);
+      tap(acc, 10 - hk, nrb2, rp_next_tap<G>(p, m, 1, 2), pf_hook1);
+      for (int j = 3; j < k; ++j) tap(acc, 8 + j - hk, nrb2, rp_next_tap<G>(p, m, 1, j), no_hook);
       RP_T(te);
       // ---- epilogue: state + c2 + b2 (rows past the clip end are dropped)
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb) {
-        const int c0 = (2 * wc + cb) * 16 + 4 * (lane >> 4);
-        const f32x4 bias = *reinterpret_cast<const f32x4*>(bias_lds + (kMaxGroup + m) * C + c0);
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-          if (i >= nrb2) break;
-          const int q = r0 + (wr + WR * i) * 16 + l15;
-          const f32x4 v = res[i][cb] + (acc[i][cb] + bias);
-          if constexpr (!MEAN) {
-            if (q < L) *reinterpret_cast<f32x4*>(p.dst[m] + cb0 + (long long)q * C + c0) = v;
-          } else if (m == 0) {
-            macc[i][cb] = v;
-          } else if (!last_m) {
-            macc[i][cb] = macc[i][cb] + v;
-          } else {
-            const f32x4 mv = (macc[i][cb] + v) / 3.0f;
-            f32x4 sv;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sv[e] = rp_silu(mv[e]);
-            if (q < L) *reinterpret_cast<f32x4*>(p.mean_out + cb0 + (long long)q * C + c0) = sv;
-          }
-        }
-      }
+      rp_epilogue<A, G, C, MEAN>(p, bias_lds + (kMaxGroup + m) * C, acc, res, macc, ln, m, cb0, r0, nrb2);
       RP_T(tf);
       if (has_next) {
         rp_barrier();  // every wave's T reads are done before the next S image overwrites them
-        commit_fill(nsr0);
+        rp_fill_commit<A, G>(lds, pf, nsr0, L, tid);
         rp_barrier();
       }
-#ifdef RP_DIAG_STAMPS
-      {
+      RP_STAMP({
         RP_T(tg);
-        dg[0] += tb - ta; dg[1] += tc - tb; dg[2] += te - tc; dg[3] += tf - te; dg[4] += tg - tf;
-        dg[5] += 1; dg[6] += k; dg[7] += k;
-      }
-#endif
+        st.member(ta, tb, tc, te, tf, tg, k);
+      })
     }
-    if (!more) break;
-    tile = next_tile;
-    b = nb;
-    r0 = nr0;
+    if (!tl.more) break;
+    tl.advance();
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last tap's (unused) fragment reloads
-#ifdef RP_DIAG_STAMPS
-  if (tid == 0)
-    for (int i = 0; i < 16; ++i) atomicAdd(&g_rp_diag[(C == 64 ? 16 : 0) + i], dg[i]);
-#endif
+  RP_STAMP(st.flush(C, tid);)
 }
 
 // conv_res_pair_h3 (round 5): conv_res_pair_g in h3 arithmetic (ResPairParams::h3; the fp16 h / l
@@ -731,13 +369,12 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair_g(const ResPairParams p)
 template <int C, bool MEAN, int RR = kRp3Rows<C>, bool RING = false>
 __global__ void __launch_bounds__(512, 1) conv_res_pair_h3(const ResPairParams p) {
 #ifdef __HIP_DEVICE_COMPILE__  // the body is device code only (its host pass dropped the RING stubs)
-  using G = RpGeom3<C, RR>;
-  constexpr int R = G::R, WR = G::WR, RB = G::RB1, PS = G::PS;
-  constexpr int G8 = G::G8, NIT = G::NIT, NS = G::NS;
-  constexpr int NCH = G::NCH, IMG = G::IMG, WTAP = G::WTAP;
+  using A = RpH3;
+  using G = RpGeom<A, C, RR>;
+  constexpr int NCH = G::NCH, WR = G::WR, RB = G::RB1, PS = G::PS, IMG = G::IMG, NIT = G::NIT, WTAP = G::WTAP;
   // RING (round 6, Knobs::rp_ring): the weight taps through an LDS ring of NSLOT taps instead of
   // per-wave loads (below)
-  constexpr int NSLOT = 4, RINGB = RING ? NSLOT * WTAP : 0, BIASB = 2 * kMaxGroup * C * 4;
+  constexpr int NSLOT = 4, RINGB = RING ? NSLOT * WTAP : 0, BIASB = G::BIASB;
   constexpr int NP = C * C / 256, PPW = (NP + 7) / 8;  // 1 KiB pieces per tap, per wave
   static_assert(IMG + RINGB + BIASB + 2 * NSLOT * 4 <= 160 * 1024, "LDS");
   __shared__ __attribute__((aligned(16))) char lds[IMG + RINGB + BIASB + (RING ? 2 * NSLOT * 4 : 0)];
@@ -747,73 +384,14 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair_h3(const ResPairParams p
   unsigned* const rd_cnt = reinterpret_cast<unsigned*>(lds + IMG + RINGB + BIASB);
   unsigned* const full_cnt = rd_cnt + NSLOT;
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wc = wave % G::WC, wr = wave / G::WC;
-  const int l15 = lane & 15, kg = lane >> 4;
+  const RpLane ln = RpLane::make<G>();
+  const int tid = ln.tid, lane = ln.lane, wave = ln.wave, wc = ln.wc, wr = ln.wr;
   const int L = p.L, nmem = p.nmem;
-  const int ntl = (L + R - 1) / R;
-  const int total = ntl * p.batch;
 
-  // ---- S image fill (as conv_res_pair) ----
-  f32x4 pf[NIT][2];
-  auto issue_fill_item = [&](const float* src, int r0, int k) {
-    const int it = min(tid + 512 * k, NS * G8 - 1);
-    const int s = ((it >> 3) / G8) * 8 + (it & 7), g8 = (it >> 3) % G8;
-    const int a = min(max(r0 - 8 - G::H1 + s, 0), L - 1);
-    const f32x4* q = reinterpret_cast<const f32x4*>(src + (long long)a * C + g8 * 8);
-    pf[k][0] = q[0];
-    pf[k][1] = q[1];
-  };
-  // sc: the image's range scale, 2^h2_shift(max |state| of the clip) (dcx_kernels.h)
-  auto commit_fill = [&](int r0, float sc) {
-#pragma unroll
-    for (int k = 0; k < NIT; ++k) {
-      const int it = tid + 512 * k;
-      if (!(NIT * 512 == NS * G8 || it < NS * G8)) continue;
-      const int s = ((it >> 3) / G8) * 8 + (it & 7), g8 = (it >> 3) % G8;
-      const int a = r0 - 8 - G::H1 + s;
-      const bool ok = a >= 0 && a < L;
-      s16x8 hv, lv;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) {
-        const float sv = rp_silu(pf[k][e >> 2][e & 3]) * sc;
-        const float v = ok ? sv : 0.f;
-        unsigned short hh, ll;
-        split2h_nc(v, hh, ll);
-        hv[e] = (short)hh;
-        lv[e] = (short)ll;
-      }
-      char* d = lds + ((g8 >> 2) * 8 + (g8 & 3)) * PS + s * 16;
-      *reinterpret_cast<s16x8*>(d) = hv;
-      *reinterpret_cast<s16x8*>(d + 4 * PS) = lv;
-    }
-  };
-
-  // ---- weight fragments of chunk ch of a tap ([chunk][Cout][128 B], the ConvParams::w3 tap slice):
-  // [column block][h' | l'] of the lane's channel group ----
-  s16x8 wf[NCH][2][2];
-  const int wo0 = ((2 * wc) * 16 + l15) * 128 + kg * 32, wo1 = wo0 + 16;
-  [[maybe_unused]] bool wl_off = false;  // -DRP_DIAG_NOWLOAD (timing only, wrong results): no reloads after the prologue
-  auto load_wf = [&](const unsigned short* wtap, int ch) {
-#ifdef RP_DIAG_NOWLOAD
-    if (wl_off) return;
-#endif
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)wtap, 0, WTAP, 0x00020000);
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb) {
-      const int so = (ch * C + cb * 16) * 128;
-      wf[ch][cb][0] = __builtin_bit_cast(s16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, wo0, so, 0));
-      wf[ch][cb][1] = __builtin_bit_cast(s16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, wo1, so, 0));
-    }
-  };
-  // the tap after tap j of conv `conv` of member m: the stream runs c1, c2 of each member, then
-  // member 0 again (the next tile; past the last tile harmless loads of weights already used)
-  auto next_tap = [&](int m, int conv, int j) -> const unsigned short* {
-    if (RING) return nullptr;
-    if (j + 1 < p.taps[m]) return (conv ? p.w2[m] : p.w1[m]) + (long long)(j + 1) * (WTAP / 2);
-    if (conv == 0) return p.w2[m];
-    return p.w1[m + 1 < nmem ? m + 1 : 0];
-  };
+  f32x4 pf[NIT][2];      // the next S image's rows in flight
+  s16x8 wf[NCH][2][2];  // the weight fragments of a tap, [chunk][column block][h' | l'] of the lane's channel group
+  const A::Wo wo = A::wo(lane, wc);
+  const A::Xb xl = A::xlane<G::NS>(lds, lane);
 
   // ---- RING: the weight stream through LDS.  Tap t (counted over the whole kernel: c1 then c2 of
   // each member, tile after tile) sits in slot t % NSLOT as NP pieces of 1 KiB, piece (ch, column
@@ -837,7 +415,7 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair_h3(const ResPairParams p
   for (int i = 0; i < PPW; ++i) {
     const int pc = min(wave + 8 * i, NP - 1);
     const int pl = pc & 1, cbk = (pc >> 1) % (C / 16), ch = (pc >> 1) / (C / 16);
-    dsrc[i] = (ch * C + cbk * 16 + l15) * 128 + kg * 32 + pl * 16;
+    dsrc[i] = (ch * C + cbk * 16 + ln.l15) * 128 + (lane >> 4) * 32 + pl * 16;
   }
   // members' weights and tap counts picked by uniform selects (an index into the kernel-argument
   // arrays became a vector load that hipcc then waited for with vmcnt(0), DMA in flight included)
@@ -890,15 +468,10 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair_h3(const ResPairParams p
   // ---- one tap, chunk-major: the MFMAs of chunk ch for every row block of the wave, then chunk ch
   // of the next tap into the fragment registers; hook() once every reload of the tap is issued (its
   // loads are then younger than the fragments the next tap waits for) ----
-  // lane parts of the two activation reads (h and l pieces of the lane's channel group, row within
-  // the 16-row block); a tap adds its wave-uniform row offset once, row block / chunk offsets are
-  // instruction immediates
-  const int pkh = (kg * NS + l15) * 16, pkl = ((4 + kg) * NS + l15) * 16;
   // RING: hook() first (its nyoung global loads are then the only ones younger than the pieces B
   // waits for; nyoung may undercount, never overcount)
-  auto tap = [&](f32x4 (&acc)[RB][2], int rowoff, int nrb, const unsigned short* wnext, int nyoung, auto hook) {
-    const int tb = (wr * 16 + rowoff) * 16;
-    const char *xbh = lds + pkh + tb, *xbl = lds + pkl + tb;
+  auto tap = [&](RpRow (&acc)[RB], int rowoff, int nrb, const unsigned short* wnext, int nyoung, auto hook) {
+    const A::Xb x = A::at(xl, (wr * 16 + rowoff) * 16);
     const int t = ring_t;
     if constexpr (RING) {
       hook();
@@ -915,26 +488,13 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair_h3(const ResPairParams p
     for (int ch = 0; ch < NCH; ++ch) {
 #pragma unroll
       for (int i = 0; i < RB; ++i) {
-        if (i < nrb) {
-          const int io = (WR * 16 * i) * 16 + ch * 8 * PS;
-          const s16x8 xl = *reinterpret_cast<const s16x8*>(xbl + io);
-          const s16x8 xh = *reinterpret_cast<const s16x8*>(xbh + io);
-#pragma unroll
-          for (int cb = 0; cb < 2; ++cb) {
-            acc[i][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wf[ch][cb][0]),
-                                                                __builtin_bit_cast(f16x8, xl), acc[i][cb], 0, 0, 0);
-            acc[i][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wf[ch][cb][1]),
-                                                                __builtin_bit_cast(f16x8, xh), acc[i][cb], 0, 0, 0);
-            acc[i][cb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wf[ch][cb][0]),
-                                                                __builtin_bit_cast(f16x8, xh), acc[i][cb], 0, 0, 0);
-          }
-        }
+        if (i < nrb) rp_block<A>(acc[i], wf[ch], x, (WR * 16 * i) * 16 + ch * A::PPC * PS);
       }
       if constexpr (RING) {
         if (ch == 0) spin_ge(full_cnt + (t + 1) % NSLOT, 8u * (unsigned)((t + 1) / NSLOT + 1));
         read_wf((t + 1) % NSLOT, ch);
       } else {
-        load_wf(wnext, ch);
+        rp_load_wf<A, G, C>(wf[ch], wnext, ch, wo);
       }
       // keep the reloads here: left to itself the scheduler sinks all of them to the end of the tap,
       // and the next tap's first MFMAs then wait a whole L2 round trip
@@ -944,6 +504,7 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair_h3(const ResPairParams p
     if constexpr (!RING) hook();
   };
   auto no_hook = [] {};
+  auto next_tap = [&](int m, int conv, int j) { return RING ? nullptr : rp_next_tap<G>(p, m, conv, j); };
 
   // c2 computes every row block (the waves owning fewer than RB of the R output rows compute rows past
   // them, from image rows inside the image, and drop them in the epilogue): a runtime row-block count
@@ -972,13 +533,9 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair_h3(const ResPairParams p
     }
     shs0n = __builtin_amdgcn_readfirstlane(h2_shift(an));
   };
-  int tile = blockIdx.x;
-  if (tile >= total) return;  // whole workgroup, before any barrier
-  int b = tile / ntl, r0 = (tile - b * ntl) * R;
-  if (tid < 2 * nmem * C) {
-    const int conv = tid / (nmem * C), m = (tid / C) % nmem, c = tid % C;
-    bias_lds[(conv * kMaxGroup + m) * C + c] = (conv ? p.b2[m] : p.b1[m])[c];
-  }
+  RpTiles<G::R> tl;
+  if (!tl.first(p)) return;  // whole workgroup, before any barrier
+  rp_bias_prologue<C>(bias_lds, p, tid);
   if constexpr (RING) {
     if (tid < 2 * NSLOT) rd_cnt[tid] = 0u;
     rp_barrier();
@@ -986,11 +543,11 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair_h3(const ResPairParams p
     ring_issue(1);
   } else {
 #pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) load_wf(p.w1[0], ch);
+    for (int ch = 0; ch < NCH; ++ch) rp_load_wf<A, G, C>(wf[ch], p.w1[0], ch, wo);
   }
 #pragma unroll
-  for (int k = 0; k < NIT; ++k) issue_fill_item(p.src[0] + (long long)b * p.bstride, r0, k);
-  commit_fill(r0, __builtin_ldexpf(1.0f, s_shift(0, b)));
+  for (int k = 0; k < NIT; ++k) rp_fill_issue<G, C>(pf[k], p.src[0] + (long long)tl.b * p.bstride, tl.r0, L, tid, k);
+  rp_fill_commit<A, G>(lds, pf, tl.r0, L, tid, __builtin_ldexpf(1.0f, s_shift(0, tl.b)));
   if constexpr (RING) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     count_in(full_cnt + 0);  // tap 1's pieces are counted in by B of tap 0
@@ -1000,61 +557,29 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair_h3(const ResPairParams p
 #pragma unroll
     for (int ch = 0; ch < NCH; ++ch) read_wf(0, ch);
   }
-  wl_off = true;
-  f32x4 macc[MEAN ? RB : 1][2];
-#ifdef RP_DIAG_STAMPS
-  unsigned long long dg[16] = {};
-#endif
+  RpRow macc[MEAN ? RB : 1];
+  RP_STAMP(RpStamps st;)
   for (;;) {
-    const int next_tile = tile + gridDim.x;
-    const bool more = next_tile < total;
-    const int nb = more ? next_tile / ntl : 0, nr0 = more ? (next_tile - nb * ntl) * R : 0;
-    if constexpr (RING) tile_shifts(b, nb);
+    tl.look_ahead();
+    const int b = tl.b, r0 = tl.r0;
+    if constexpr (RING) tile_shifts(b, tl.nb);
     for (int m = 0; m < nmem; ++m) {
       const int k = p.taps[m], hk = (k - 1) >> 1, d = p.dil[m];
       const long long cb0 = (long long)b * p.bstride;
       const bool last_m = m + 1 == nmem;
-      const bool has_next = !last_m || more;
-      f32x4 acc[RB][2];
+      const bool has_next = !last_m || tl.more;
+      RpRow acc[RB];
       RP_T(ta);
       // ---- c1 over rows [r0 - 8, r0 + R + 8) from the S image
 #pragma unroll
-      for (int i = 0; i < RB; ++i) acc[i][0] = acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      const int ts = p.tap_sync;
-      for (int j = 0; j < k; ++j) {
-        tap(acc, G::H1 + (j - hk) * d, RB, next_tap(m, 0, j), 0, no_hook);
-        if (ts && (j + 1) % ts == 0 && j + 1 < k) rp_barrier();  // workgroup-uniform
-      }
+      for (int i = 0; i < RB; ++i) acc[i].zero();
+      for (int j = 0; j < k; ++j) tap(acc, G::H1 + (j - hk) * d, RB, next_tap(m, 0, j), 0, no_hook);
       RP_T(tb);
       rp_barrier();  // every wave's S reads are done before T overwrites them
-      // ---- T image: silu(c1 + b1) as h / l over the S image (zero outside the clip), range-scaled
+      // ---- T image, range-scaled (rigorous bound: no per-element check, epilogue_lds)
       const int sh_t = RING ? mpick(sht[0], sht[1], sht[2], m) : t_shift(m, b);
       const float us1 = __builtin_ldexpf(1.0f, -(p.w3_shift1[m] + (RING ? mpick(shs[0], shs[1], shs[2], m) : s_shift(m, b))));
-      const float tsc = __builtin_ldexpf(1.0f, sh_t);  // (rigorous bound: no per-element check, epilogue_lds)
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb) {
-        const int c0 = (2 * wc + cb) * 16 + 4 * (lane >> 4);
-        const f32x4 bias = *reinterpret_cast<const f32x4*>(bias_lds + m * C + c0);
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-          const int ir = (wr + WR * i) * 16 + l15, a = r0 - 8 + ir;
-          const bool ok = a >= 0 && a < L;
-          s16x4 hv, lv;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float pre = acc[i][cb][e] * us1 + bias[e];
-            const float sv = rp_silu(pre);
-            const float v = ok ? sv * tsc : 0.f;
-            unsigned short hh, ll;
-            split2h_nc(v, hh, ll);
-            hv[e] = (short)hh;
-            lv[e] = (short)ll;
-          }
-          char* dst = lds + ((c0 >> 5) * 8 + ((c0 >> 3) & 3)) * PS + ir * 16 + (c0 & 7) * 2;
-          *reinterpret_cast<s16x4*>(dst) = hv;
-          *reinterpret_cast<s16x4*>(dst + 4 * PS) = lv;
-        }
-      }
+      rp_t_image<A, G, C>(lds, bias_lds + m * C, acc, ln, r0, L, us1, __builtin_ldexpf(1.0f, sh_t));
       rp_barrier();
       RP_T(tc);
       // ---- c2 over rows [r0, r0 + R) from the T image.  Tap 0 loads the residual rows, taps 1 and 2
@@ -1062,355 +587,64 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair_h3(const ResPairParams p
       // tap's fragment reloads (k >= 3, so taps 0..2 exist; they are peeled so that the register
       // arrays are indexed by constants)
 #pragma unroll
-      for (int i = 0; i < RB; ++i) acc[i][0] = acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      const float* nsrc = !last_m ? p.src[m + 1] + cb0 : p.src[0] + (long long)nb * p.bstride;
-      const int nsr0 = !last_m ? r0 : nr0;
-      f32x4 res[RB][2];
+      for (int i = 0; i < RB; ++i) acc[i].zero();
+      const float* nsrc = !last_m ? p.src[m + 1] + cb0 : p.src[0] + (long long)tl.nb * p.bstride;
+      const int nsr0 = !last_m ? r0 : tl.nr0;
+      RpRow res[RB];
       float dcur = 0.f;  // this clip's running max |dst| (range_report)
       auto res_hook = [&] {
         if constexpr (!MEAN) dcur = range_cur(p.dst_amax[m], b);  // older than the residual loads
 #pragma unroll
-        for (int i = 0; i < RB; ++i) {
-          const int q = min(r0 + (wr + WR * i) * 16 + l15, L - 1);
-#pragma unroll
-          for (int cb = 0; cb < 2; ++cb) {
-            const int c0 = (2 * wc + cb) * 16 + 4 * (lane >> 4);
-            res[i][cb] = *reinterpret_cast<const f32x4*>(p.src[m] + cb0 + (long long)q * C + c0);
-          }
-        }
+        for (int i = 0; i < RB; ++i) rp_load_res<G, C>(res[i], p.src[m] + cb0, ln, r0, L, i);
+      };
+      // RING at C = 32: the empty asm makes tid opaque, so the items' image rows are computed here and
+      // not hoisted out of the tile loop.  Hoisted, conv_res_pair_h3<32,mean,624,ring> spilled them and
+      // reloaded them here from scratch, and each reload's vmcnt(0) wait took the weight DMA in flight
+      // with it (3 reloads in the c2 taps: 3.24 ms per launch on the C2 bench against 3.02 with the asm;
+      // scratch 120 -> 64 bytes per lane).  At C = 64 nothing was spilled and the recomputed item math
+      // cost 0.7 % (conv_res_pair_h3<64,ring> 10.12 against 10.05 ms), so it keeps the plain tid.
+      auto pf_tid = [&] {
+        int t = tid;
+        if constexpr (RING && C == 32) asm volatile("" : "+v"(t));
+        return t;
       };
       auto pf_hook0 = [&] {
-        if (!has_next) return;
-#pragma unroll
-        for (int kk = 0; kk < NIT / 2; ++kk) issue_fill_item(nsrc, nsr0, kk);
+        if (has_next) rp_fill_issue_range<G, C, 0, NIT / 2>(pf, nsrc, nsr0, L, pf_tid());
       };
       auto pf_hook1 = [&] {
-        if (!has_next) return;
-#pragma unroll
-        for (int kk = NIT / 2; kk < NIT; ++kk) issue_fill_item(nsrc, nsr0, kk);
+        if (has_next) rp_fill_issue_range<G, C, NIT / 2, NIT>(pf, nsrc, nsr0, L, pf_tid());
       };
       tap(acc, 8 - hk, RB, next_tap(m, 1, 0), RB * 2, res_hook);
-      if (ts == 1) rp_barrier();
       tap(acc, 9 - hk, RB, next_tap(m, 1, 1), has_next ? (NIT / 2) * 2 : 0, pf_hook0);
-      if (ts && 2 % ts == 0) rp_barrier();
       tap(acc, 10 - hk, RB, next_tap(m, 1, 2), has_next ? (NIT - NIT / 2) * 2 : 0, pf_hook1);
-      if (ts && 3 % ts == 0 && 3 < k) rp_barrier();
-      for (int j = 3; j < k; ++j) {
-        tap(acc, 8 + j - hk, RB, next_tap(m, 1, j), 0, no_hook);
-        if (ts && (j + 1) % ts == 0 && j + 1 < k) rp_barrier();
-      }
+      for (int j = 3; j < k; ++j) tap(acc, 8 + j - hk, RB, next_tap(m, 1, j), 0, no_hook);
       RP_T(te);
-      // ---- epilogue: state + c2 + b2 (rows past the clip end are dropped); its max |.| per clip for
-      // the next pair's S image
+      // ---- epilogue; its max |.| per clip for the next pair's S image
       const float us2 = __builtin_ldexpf(1.0f, -(p.w3_shift2[m] + sh_t));
-      float dmax = 0.f;
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb) {
-        const int c0 = (2 * wc + cb) * 16 + 4 * (lane >> 4);
-        const f32x4 bias = *reinterpret_cast<const f32x4*>(bias_lds + (kMaxGroup + m) * C + c0);
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-          if (i >= nrb2) break;
-          const int q = r0 + (wr + WR * i) * 16 + l15;
-          const f32x4 v = res[i][cb] + (acc[i][cb] * us2 + bias);
-          if constexpr (!MEAN) {
-            if (q < L) {
-              *reinterpret_cast<f32x4*>(p.dst[m] + cb0 + (long long)q * C + c0) = v;
-              dmax = fmaxf(dmax, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
-            }
-          } else if (m == 0) {
-            macc[i][cb] = v;
-          } else if (!last_m) {
-            macc[i][cb] = macc[i][cb] + v;
-          } else {
-            const f32x4 mv = (macc[i][cb] + v) / 3.0f;
-            f32x4 sv;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sv[e] = rp_silu(mv[e]);
-            if (q < L) *reinterpret_cast<f32x4*>(p.mean_out + cb0 + (long long)q * C + c0) = sv;
-          }
-        }
-      }
+      [[maybe_unused]] const float dmax =
+          rp_epilogue<A, G, C, MEAN>(p, bias_lds + (kMaxGroup + m) * C, acc, res, macc, ln, m, cb0, r0, nrb2, us2);
       if constexpr (!MEAN) {
         if (p.dst_amax[m]) range_report(dmax, p.dst_amax[m], b, __builtin_inff(), nullptr, dcur);  // workgroup-uniform
       }
       RP_T(tf);
       if (has_next) {
         rp_barrier();  // every wave's T reads are done before the next S image overwrites them
-        commit_fill(nsr0, __builtin_ldexpf(1.0f, RING ? (last_m ? shs0n : mpick(shs[1], shs[2], shs[2], m))
-                                                 : last_m ? s_shift(0, nb) : s_shift(m + 1, b)));
+        rp_fill_commit<A, G>(lds, pf, nsr0, L, tid,
+                             __builtin_ldexpf(1.0f, RING ? (last_m ? shs0n : mpick(shs[1], shs[2], shs[2], m))
+                                                    : last_m ? s_shift(0, tl.nb) : s_shift(m + 1, b)));
         rp_barrier();
       }
-#ifdef RP_DIAG_STAMPS
-      {
+      RP_STAMP({
         RP_T(tg);
-        dg[0] += tb - ta; dg[1] += tc - tb; dg[2] += te - tc; dg[3] += tf - te; dg[4] += tg - tf;
-        dg[5] += 1; dg[6] += k; dg[7] += k;
-      }
-#endif
+        st.member(ta, tb, tc, te, tf, tg, k);
+      })
     }
-    if (!more) break;
-    tile = next_tile;
-    b = nb;
-    r0 = nr0;
+    if (!tl.more) break;
+    tl.advance();
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last tap's (unused) fragment reloads
-#ifdef RP_DIAG_STAMPS
-  if (tid == 0)
-    for (int i = 0; i < 16; ++i) atomicAdd(&g_rp_diag[(C == 64 ? 16 : 0) + i], dg[i]);
+  RP_STAMP(st.flush(C, tid);)
 #endif
-#endif
-}
-
-
-// conv_res_pair_w4 (round 5): the barrier-free tap loops of conv_res_pair_g on 4-wave workgroups, TWO
-// per CU.  In the 8-wave kernels the two waves of a SIMD belong to one workgroup and go through the
-// same phases together: both run their tap loops (sharing the matrix pipe, each covering the other's
-// LDS latency only while both are there), then both convert images (VALU only, the matrix pipe idle),
-// then both wait at the hand-off barriers for the slowest wave (PMC: 0.40-0.50 MFMA busy; stamps of
-// the 8-wave barrier-free kernel: taps at 0.92 of MFMA issue for the leading wave, the lagging wave's
-// deficit paid at the next barrier).  Here the partner wave on each SIMD belongs to ANOTHER workgroup,
-// with its own LDS image and barriers, so one workgroup's image conversions, epilogue, S-image loads
-// and barrier waits run beside the other's MFMAs.  Each workgroup owns R output rows of one clip (its
-// image within half the LDS); the S image is filled only over the rows member m's c1 reads (its reach
-// (k - 1) / 2 * d), straight from global memory (the other workgroup covers the load latency).  The
-// MFMAs, their order per accumulator and the layouts are conv_res_pair_g's, so the bits are the same.
-template <int C, int RR>
-struct RpGeom4 {
-  static constexpr int R = RR;
-  static constexpr int M1 = R + 16;               // c1 rows: [r0 - 8, r0 + R + 8)
-  static constexpr int H1 = 32;                   // largest c1 reach
-  static constexpr int NS = M1 + 2 * H1;          // S image rows
-  static constexpr int NCH = C / 16;
-  static constexpr int WC = C / 32, WR = 4 / WC;  // waves: WR row groups x WC column halves
-  static constexpr int NB1 = M1 / 16, RB = NB1 / WR;
-  static constexpr int NB2 = R / 16;
-  static constexpr int PS = NS * 16;
-  static constexpr int IMG = NCH * 6 * PS;
-  static constexpr int G8 = C / 8;
-  static constexpr int WTAP = C * C * 6;
-  static constexpr int FB = 4;                    // S-image items (8 channels) per thread per load batch
-  static constexpr int LDS = IMG + 2 * kMaxGroup * C * 4;
-  static_assert(NB1 % WR == 0 && (NB2 + WR - 1) / WR <= RB, "row blocks per wave");
-  static_assert(LDS <= 80 * 1024, "two workgroups per CU");
-};
-template <int C>
-constexpr int kRp4Rows = C == 32 ? 304 : 112;
-
-template <int C, bool MEAN, int RR = kRp4Rows<C>>
-__global__ void __launch_bounds__(256, 2) conv_res_pair_w4(const ResPairParams p) {
-  using G = RpGeom4<C, RR>;
-  constexpr int R = G::R, NCH = G::NCH, WR = G::WR, RB = G::RB, PS = G::PS, IMG = G::IMG;
-  constexpr int G8 = G::G8, NS = G::NS, WTAP = G::WTAP, FB = G::FB;
-  __shared__ __attribute__((aligned(16))) char lds[G::LDS];
-  float* const bias_lds = reinterpret_cast<float*>(lds + IMG);  // [conv][member][C]
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wc = wave % G::WC, wr = wave / G::WC;
-  const int l15 = lane & 15, hf = (lane >> 4) & 1, t = lane >> 5;
-  const int L = p.L, nmem = p.nmem;
-  const int ntl = (L + R - 1) / R;
-  const int total = ntl * p.batch;
-
-  // ---- S image: silu(state) as planes over the 8-row groups covering [H1 - reach, H1 + M1 + reach)
-  // (zero outside the clip = the conv's padding); rows outside that range are never read ----
-  auto fill = [&](const float* src, int r0, int reach) {
-    const int lo = (G::H1 - reach) & ~7;
-    const int hi = min(NS, (G::H1 + G::M1 + reach + 7) & ~7);
-    const int nit = (hi - lo) * G8;
-    for (int base = 0; base < nit; base += 256 * FB) {
-      f32x4 v[FB][2];
-#pragma unroll
-      for (int k = 0; k < FB; ++k) {  // unconditional loads (index clamped): all in flight at once
-        const int it = min(base + tid + 256 * k, nit - 1);
-        const int s = lo + ((it >> 3) / G8) * 8 + (it & 7), g8 = (it >> 3) % G8;
-        const int a = min(max(r0 - 8 - G::H1 + s, 0), L - 1);
-        const f32x4* q = reinterpret_cast<const f32x4*>(src + (long long)a * C + g8 * 8);
-        v[k][0] = q[0];
-        v[k][1] = q[1];
-      }
-#pragma unroll
-      for (int k = 0; k < FB; ++k) {
-        const int it = base + tid + 256 * k;
-        if (it < nit) {
-          const int s = lo + ((it >> 3) / G8) * 8 + (it & 7), g8 = (it >> 3) % G8;
-          const int a = r0 - 8 - G::H1 + s;
-          const bool ok = a >= 0 && a < L;
-          s16x8 hv, mv, lv;
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            const float sv = rp_silu(v[k][e >> 2][e & 3]);
-            const float x = ok ? sv : 0.f;
-            unsigned short h, m, l;
-            split3(x, h, m, l);
-            hv[e] = (short)h;
-            mv[e] = (short)m;
-            lv[e] = (short)l;
-          }
-          char* d = lds + ((g8 >> 1) * 6 + (g8 & 1) * 3) * PS + s * 16;
-          *reinterpret_cast<s16x8*>(d) = hv;
-          *reinterpret_cast<s16x8*>(d + PS) = mv;
-          *reinterpret_cast<s16x8*>(d + 2 * PS) = lv;
-        }
-      }
-    }
-  };
-
-  // ---- weight fragments, one tap ahead (conv_res_pair_g) ----
-  s16x8 wf[NCH][2][2];
-  // buffer loads: the lane offsets are loop-invariant VGPRs, the tap base a scalar resource and the
-  // chunk / column-block offsets scalar constants, so a reload costs no address arithmetic
-  const int wo0 = ((2 * wc) * 16 + l15) * 96 + hf * 48 + t * 16, wo1 = ((2 * wc) * 16 + l15) * 96 + hf * 48 + (t ? 32 : 0);
-  auto load_wf = [&](const unsigned short* wtap, int ch) {
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)wtap, 0, WTAP, 0x00020000);
-#pragma unroll
-    for (int cb = 0; cb < 2; ++cb) {
-      const int so = (ch * C + cb * 16) * 96;
-      wf[ch][cb][0] = __builtin_bit_cast(s16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, wo0, so, 0));
-      wf[ch][cb][1] = __builtin_bit_cast(s16x8, __builtin_amdgcn_raw_buffer_load_b128(rw, wo1, so, 0));
-    }
-  };
-  auto next_tap = [&](int m, int conv, int j) -> const unsigned short* {
-    if (j + 1 < p.taps[m]) return (conv ? p.w2[m] : p.w1[m]) + (long long)(j + 1) * (WTAP / 2);
-    if (conv == 0) return p.w2[m];
-    return p.w1[m + 1 < nmem ? m + 1 : 0];
-  };
-  // lane parts of the three activation reads (piece, row within the 16-row block); a tap adds its
-  // wave-uniform row offset once, and row block / chunk offsets are instruction immediates
-  const int pk0 = ((hf * 3 + t) * NS + l15) * 16, pk1 = ((hf * 3 + (t ? 0 : 1)) * NS + l15) * 16;
-  const int pk2 = ((hf * 3 + (t ? 0 : 2)) * NS + l15) * 16;
-  auto tap = [&](f32x4 (&acc)[RB][2], int rowoff, int nrb, const unsigned short* wnext) {
-    const int tb = (wr * 16 + rowoff) * 16;
-    const char *xb0 = lds + pk0 + tb, *xb1 = lds + pk1 + tb, *xb2 = lds + pk2 + tb;
-    __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-    for (int ch = 0; ch < NCH; ++ch) {
-#pragma unroll
-      for (int i = 0; i < RB; ++i) {
-        if (i < nrb) {
-          const int io = (WR * 16 * i) * 16 + ch * 6 * PS;
-          const s16x8 x2 = *reinterpret_cast<const s16x8*>(xb2 + io);
-          const s16x8 x1 = *reinterpret_cast<const s16x8*>(xb1 + io);
-          const s16x8 x0 = *reinterpret_cast<const s16x8*>(xb0 + io);
-#pragma unroll
-          for (int cb = 0; cb < 2; ++cb) {
-            acc[i][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[ch][cb][1]),
-                                                                 __builtin_bit_cast(bf16x8, x2), acc[i][cb], 0, 0, 0);
-            acc[i][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[ch][cb][0]),
-                                                                 __builtin_bit_cast(bf16x8, x1), acc[i][cb], 0, 0, 0);
-            acc[i][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wf[ch][cb][0]),
-                                                                 __builtin_bit_cast(bf16x8, x0), acc[i][cb], 0, 0, 0);
-          }
-        }
-      }
-      load_wf(wnext, ch);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-    __builtin_amdgcn_s_setprio(0);
-  };
-
-  const int nrb2 = min(RB, (G::NB2 - wr + WR - 1) / WR);
-  int tile = blockIdx.x;
-  if (tile >= total) return;  // whole workgroup, before any barrier
-  int b = tile / ntl, r0 = (tile - b * ntl) * R;
-  for (int i = tid; i < 2 * nmem * C; i += 256) {
-    const int conv = i / (nmem * C), m = (i / C) % nmem, c = i % C;
-    bias_lds[(conv * kMaxGroup + m) * C + c] = (conv ? p.b2[m] : p.b1[m])[c];
-  }
-#pragma unroll
-  for (int ch = 0; ch < NCH; ++ch) load_wf(p.w1[0], ch);
-  f32x4 macc[MEAN ? RB : 1][2];
-  for (;;) {
-    const int next_tile = tile + gridDim.x;
-    const bool more = next_tile < total;
-    const long long cb0 = (long long)b * p.bstride;
-    for (int m = 0; m < nmem; ++m) {
-      const int k = p.taps[m], hk = (k - 1) >> 1, d = p.dil[m];
-      const bool last_m = m + 1 == nmem;
-      fill(p.src[m] + cb0, r0, hk * d);
-      rp_barrier();
-      // ---- c1 over rows [r0 - 8, r0 + R + 8) from the S image
-      f32x4 acc[RB][2];
-#pragma unroll
-      for (int i = 0; i < RB; ++i) acc[i][0] = acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      for (int j = 0; j < k; ++j) tap(acc, G::H1 + (j - hk) * d, RB, next_tap(m, 0, j));
-      rp_barrier();  // every wave's S reads are done before T overwrites them
-      // ---- T image: silu(c1 + b1) planes over the S image (zero outside the clip)
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb) {
-        const int c0 = (2 * wc + cb) * 16 + 4 * (lane >> 4);
-        const f32x4 bias = *reinterpret_cast<const f32x4*>(bias_lds + m * C + c0);
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-          const int ir = (wr + WR * i) * 16 + l15, a = r0 - 8 + ir;
-          const bool ok = a >= 0 && a < L;
-          s16x4 hv, mv, lv;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float sv = rp_silu(acc[i][cb][e] + bias[e]);
-            const float v = ok ? sv : 0.f;
-            unsigned short h, mm, l;
-            split3(v, h, mm, l);
-            hv[e] = (short)h;
-            mv[e] = (short)mm;
-            lv[e] = (short)l;
-          }
-          char* dst = lds + ((c0 >> 4) * 6 + ((c0 >> 3) & 1) * 3) * PS + ir * 16 + (c0 & 7) * 2;
-          *reinterpret_cast<s16x4*>(dst) = hv;
-          *reinterpret_cast<s16x4*>(dst + PS) = mv;
-          *reinterpret_cast<s16x4*>(dst + 2 * PS) = lv;
-        }
-      }
-      rp_barrier();
-      // ---- c2 over rows [r0, r0 + R) from the T image; the residual rows are loaded after tap 0's
-      // fragment reloads
-#pragma unroll
-      for (int i = 0; i < RB; ++i) acc[i][0] = acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
-      f32x4 res[RB][2];
-      tap(acc, 8 - hk, nrb2, next_tap(m, 1, 0));
-#pragma unroll
-      for (int i = 0; i < RB; ++i) {
-        const int q = min(r0 + (wr + WR * i) * 16 + l15, L - 1);
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-          const int c0 = (2 * wc + cb) * 16 + 4 * (lane >> 4);
-          res[i][cb] = *reinterpret_cast<const f32x4*>(p.src[m] + cb0 + (long long)q * C + c0);
-        }
-      }
-      for (int j = 1; j < k; ++j) tap(acc, 8 + j - hk, nrb2, next_tap(m, 1, j));
-      // ---- epilogue: state + c2 + b2 (rows past the clip end are dropped)
-#pragma unroll
-      for (int cb = 0; cb < 2; ++cb) {
-        const int c0 = (2 * wc + cb) * 16 + 4 * (lane >> 4);
-        const f32x4 bias = *reinterpret_cast<const f32x4*>(bias_lds + (kMaxGroup + m) * C + c0);
-#pragma unroll
-        for (int i = 0; i < RB; ++i) {
-          if (i >= nrb2) break;
-          const int q = r0 + (wr + WR * i) * 16 + l15;
-          const f32x4 v = res[i][cb] + (acc[i][cb] + bias);
-          if constexpr (!MEAN) {
-            if (q < L) *reinterpret_cast<f32x4*>(p.dst[m] + cb0 + (long long)q * C + c0) = v;
-          } else if (m == 0) {
-            macc[i][cb] = v;
-          } else if (!last_m) {
-            macc[i][cb] = macc[i][cb] + v;
-          } else {
-            const f32x4 mv = (macc[i][cb] + v) / 3.0f;
-            f32x4 sv;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) sv[e] = rp_silu(mv[e]);
-            if (q < L) *reinterpret_cast<f32x4*>(p.mean_out + cb0 + (long long)q * C + c0) = sv;
-          }
-        }
-      }
-      rp_barrier();  // every wave's T reads are done before the next S image overwrites them
-    }
-    if (!more) break;
-    tile = next_tile;
-    b = tile / ntl;
-    r0 = (tile - b * ntl) * R;
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the last tap's (unused) fragment reloads
 }
 
 #ifdef RP_DIAG_STAMPS
@@ -1437,24 +671,19 @@ hipError_t launch_res_pair(const ResPairParams& p, hipStream_t s, const char** k
   const Knobs& kn = p.kn ? *p.kn : kDefault;
   const int cus = device_cus();
   // C = 32: the barrier-free conv_res_pair_g, C = 64: the step schedule; Knobs (A/B and
-  // tests): rp_old runs the step schedule at C = 32 too, rp_g64 the barrier-free kernel at C = 64,
-  // rp_w4 conv_res_pair_w4 (two 4-wave workgroups per CU: same bits, measured 2-6 % slower)
-  const bool w4 = kn.rp_w4 && !kn.rp_old && !kn.rp_g64 && !p.h3;
-  const int slots = w4 ? 2 * cus : cus;
+  // tests): rp_old runs the step schedule at C = 32 too, rp_g64 the barrier-free kernel at C = 64
   // rows per tile: the default unless a smaller tile finishes the launch sooner, by rounds of tiles
-  // over the workgroup slots times a tile's rows (c1 rows R + 16, c2 rows R, ~64 rows' worth of fixed
+  // over the CUs (one workgroup each) times a tile's rows (c1 rows R + 16, c2 rows R, ~64 rows' worth of fixed
   // cost); Knobs::rp_rows forces one of the instantiated sizes.  Every size gives the same bits.
   static constexpr int kW8_32[3] = {496, 240, 112}, kW8_64[3] = {176, 112, 48};
   static constexpr int kH3_32[3] = {624, 240, 112}, kH3_64[3] = {240, 112, 48};
-  static constexpr int kW4_32[3] = {304, 112, 48}, kW4_64[3] = {112, 48, 48};
-  const int* sizes = p.h3 ? (p.C == 32 ? kH3_32 : kH3_64)
-                     : w4 ? (p.C == 32 ? kW4_32 : kW4_64) : (p.C == 32 ? kW8_32 : kW8_64);
+  const int* sizes = p.h3 ? (p.C == 32 ? kH3_32 : kH3_64) : (p.C == 32 ? kW8_32 : kW8_64);
   int si = 0;
   long long best = -1;
   for (int i = 0; i < 3; ++i) {
     const int r = sizes[i];
     const long long tiles = (long long)((p.L + r - 1) / r) * p.batch;
-    const long long cost = (tiles + slots - 1) / slots * (2LL * r + 16 + 64);
+    const long long cost = (tiles + cus - 1) / cus * (2LL * r + 16 + 64);
     if (best < 0 || cost < best) {
       best = cost;
       si = i;
@@ -1465,16 +694,14 @@ hipError_t launch_res_pair(const ResPairParams& p, hipStream_t s, const char** k
   const int R = sizes[si];
   const long long total = (long long)((p.L + R - 1) / R) * p.batch;
   if (total > (1LL << 30)) return hipErrorInvalidValue;
-  const unsigned grid = (unsigned)std::min<long long>(total, slots);  // resident workgroups (LDS)
-  ResPairParams q = p;
-  q.tap_sync = std::max(0, kn.rp_sync);
+  const unsigned grid = (unsigned)std::min<long long>(total, cus);  // resident workgroups (LDS)
   const bool mean = p.mean_out != nullptr;
   // profile names are string literals (no shared buffer between threads)
 #define DCX_RP_GO(KERN, CC, RR, NAME, ...)                                                  \
   do {                                                                                      \
     if (kname) *kname = mean ? #KERN "<" #CC ",mean" NAME ">" : #KERN "<" #CC NAME ">";     \
-    if (mean) hipLaunchKernelGGL((KERN<CC, true, RR __VA_ARGS__>), dim3(grid), dim3(w4 ? 256 : 512), 0, s, q);   \
-    else hipLaunchKernelGGL((KERN<CC, false, RR __VA_ARGS__>), dim3(grid), dim3(w4 ? 256 : 512), 0, s, q);       \
+    if (mean) hipLaunchKernelGGL((KERN<CC, true, RR __VA_ARGS__>), dim3(grid), dim3(512), 0, s, p);   \
+    else hipLaunchKernelGGL((KERN<CC, false, RR __VA_ARGS__>), dim3(grid), dim3(512), 0, s, p);       \
   } while (0)
 #define DCX_RP_SIZES(KERN, CC, R0, R1, R2, ...)                \
   do {                                                         \
@@ -1490,9 +717,6 @@ hipError_t launch_res_pair(const ResPairParams& p, hipStream_t s, const char** k
   } else if (p.h3) {  // h3 weights: conv_res_pair_h3 (the barrier-free schedule at both widths)
     if (p.C == 32) DCX_RP_SIZES(conv_res_pair_h3, 32, 624, 240, 112);
     else DCX_RP_SIZES(conv_res_pair_h3, 64, 240, 112, 48);
-  } else if (w4) {
-    if (p.C == 32) DCX_RP_SIZES(conv_res_pair_w4, 32, 304, 112, 48);
-    else DCX_RP_SIZES(conv_res_pair_w4, 64, 112, 48, 48);
   } else if (p.C == 32 && !kn.rp_old) {
     DCX_RP_SIZES(conv_res_pair_g, 32, 496, 240, 112);
   } else if (p.C == 64 && !kn.rp_old && kn.rp_g64) {

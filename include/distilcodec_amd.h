@@ -240,7 +240,7 @@ int dcx_set_split_k(dcx_codec* h, int32_t max_splits);
 
 /* A/B and test switches of the kernel selection (no reference counterpart).  dcx_create reads them
  * ONCE from the environment variables of the same names (DCX_RP_R, DCX_RP_OLD, DCX_RP_G64,
- * DCX_RP_SYNC, DCX_RP_W4, DCX_GELU_LUT, DCX_BF16_PERSIST, DCX_BF16_REG_EPI, DCX_DWCONV_TILED,
+ * DCX_GELU_LUT, DCX_BF16_PERSIST, DCX_BF16_REG_EPI, DCX_DWCONV_TILED,
  * DCX_SPLIT_MIN_STEPS, DCX_SPLIT_GROUP_OFF; the h3 arithmetic of DCX_GEMM_X6 mode: DCX_H3,
  * DCX_H3_1X1, DCX_H3_PAIRS (0 = the x6 kernels for the wide generator convs, the ConvNeXt 1x1
  * convs, the small-C ResBlock pairs), DCX_H3_BN, DCX_H3_SPLIT, DCX_RP_RING (0 = per-wave weight loads in the h3

@@ -119,11 +119,11 @@ def test_knobs_are_per_handle(cfg, monkeypatch):
         L.dcx_destroy(h)
     # a handle created with a knob in the environment: still settable, and unknown module names are
     # rejected by the read-only dcx_module_io without writing the handle's error text
-    monkeypatch.setenv("DCX_RP_W4", "1")
+    monkeypatch.setenv("DCX_RP_G64", "1")
     h = ctypes.c_void_p()
     assert L.dcx_create(ctypes.byref(c), ctypes.byref(h)) == 0
     try:
-        assert L.dcx_set_knob(h, b"DCX_RP_W4", 0) == 0
+        assert L.dcx_set_knob(h, b"DCX_RP_G64", 0) == 0
         before = L.dcx_last_error(h)
         ci, co, r = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
         assert L.dcx_module_io(h, b"no.such.module", ctypes.byref(ci), ctypes.byref(co), ctypes.byref(r)) == \

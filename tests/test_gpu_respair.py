@@ -81,7 +81,7 @@ def test_fused_batch_invariance(engines):
 @pytest.mark.parametrize("B,T", [(1, 1), (2, 7), (3, 40), (8, 200)])
 def test_pair_kernels_same_bits(engines, B, T):
     """The shipped pair kernels (the barrier-free conv_res_pair_g at C = 32, the step schedule
-    conv_res_pair at C = 64) against conv_res_pair_w4 (DCX_RP_W4=1: 4-wave workgroups, two per CU), the
+    conv_res_pair at C = 64) against the
     step schedule at both (DCX_RP_OLD=1) and the barrier-free kernel at both (DCX_RP_G64=1), switched
     per engine with dcx_set_knob: the same MFMAs in the same order per
     accumulator, so the same bits, also over many tiles per workgroup (B=8, T=200: the persistent tile
@@ -91,7 +91,7 @@ def test_pair_kernels_same_bits(engines, B, T):
     with fused.knobs(DCX_H3_PAIRS=0):  # the x6 pair kernels (h3: conv_res_pair_h3, the default)
         a = fused.generate(z)
     outs = []
-    for kn in ({"DCX_RP_W4": 1}, {"DCX_RP_OLD": 1}, {"DCX_RP_G64": 1}):
+    for kn in ({"DCX_RP_OLD": 1}, {"DCX_RP_G64": 1}):
         with fused.knobs(DCX_H3_PAIRS=0, **kn):
             outs.append(fused.generate(z))
     torch.cuda.synchronize()
@@ -102,16 +102,16 @@ def test_pair_kernels_same_bits(engines, B, T):
 
 @pytest.mark.parametrize("B,T", [(1, 93), (2, 31), (1, 7)])
 def test_tile_rows_same_bits(engines, B, T):
-    """The pair kernels on every tile height they are instantiated for (conv_res_pair_w4: 304 / 112 / 48
-    rows at C = 32, 112 / 48 at C = 64; the 8-wave kernels: 496 / 240 / 112 at C = 32, 176 / 112 / 48
-    at C = 64), which the launcher picks by tile rounds (smaller ones for the C5 hop): every output
-    row is computed with the same arithmetic whatever the tile, so every size (DCX_RP_R) gives the
-    same bits as the default, on the w4, step-schedule and barrier-free kernels."""
+    """The pair kernels on every tile height they are instantiated for (496 / 240 / 112 rows at C = 32,
+    176 / 112 / 48 at C = 64), which the launcher picks by tile rounds (smaller ones for the C5 hop):
+    every output row is computed with the same arithmetic whatever the tile, so every size (DCX_RP_R)
+    gives the same bits as the default, on the shipped kernels, the barrier-free kernel at C = 64
+    (DCX_RP_G64=1) and the step schedule at C = 32 (DCX_RP_OLD=1)."""
     fused, _ = engines
     z = _z(B, T, 500 + T)
     outs = []
-    for r in (304, 496, 240, 112, 176, 48):
-        for kn in ({}, {"DCX_RP_W4": 1}, {"DCX_RP_OLD": 1}):
+    for r in (496, 240, 112, 176, 48):
+        for kn in ({}, {"DCX_RP_G64": 1}, {"DCX_RP_OLD": 1}):
             with fused.knobs(DCX_H3_PAIRS=0, DCX_RP_R=r, **kn):
                 outs.append(fused.generate(z))
     torch.cuda.synchronize()
