@@ -403,10 +403,19 @@ class DistilCodec:
             wav = eng.generate(z)
         return wav[:, None, :]
 
-    def decode_from_codes_batch(self, codes_list: list, minus_token_offset: bool = True, enable_bfloat16: bool = False) -> list:
+    def decode_from_codes_batch(self, codes_list: list, minus_token_offset: bool = True, enable_bfloat16: bool = False,
+                                ragged: bool = False) -> list:
         """distil_codec.py:598-639: zero-pads to the longest list and returns one (1, 1, 256 L_max)
         tensor per clip.  Unlike the reference (which decodes only clip 0),
-        every clip is decoded."""
+        every clip is decoded.
+
+        `ragged=True` (opt-in; the default keeps the reference's semantics): one (1, 1, 256 len_b)
+        tensor per clip, each what `decode_from_codes` gives for that list alone (the padded form
+        computes a short clip's last samples from the frames code 0 decodes to).  The lists are padded
+        with -1, which is never read; IndexError for a code out of range inside a list; fp32 only
+        (ValueError with `enable_bfloat16`: the bf16 kernels do not take per-clip lengths)."""
+        if ragged:
+            return self._decode_ragged(codes_list, minus_token_offset, enable_bfloat16)
         if not codes_list:
             return []
         if minus_token_offset:
@@ -419,6 +428,19 @@ class DistilCodec:
         with self._precision(enable_bfloat16) as eng:
             wav = eng.generate(eng.vq_decode(batched))
         return [wav[i: i + 1, None, :].detach() for i in range(len(codes_list))]
+
+    def _decode_ragged(self, codes_list: list, minus_token_offset: bool, enable_bfloat16: bool) -> list:
+        from .ragged import check_codes_in_lengths, pad_code_lists
+        if enable_bfloat16:
+            raise ValueError("decode_from_codes_batch(ragged=True) runs in fp32 only: the bf16 kernels are not length-aware")
+        if minus_token_offset:
+            codes_list = [[c - self.tokens_id_offset for c in codes] for codes in codes_list]
+        codes, lengths = pad_code_lists(codes_list)
+        check_codes_in_lengths(codes, lengths, self.quantizer_config.codebook_size)
+        eng = self._engine()
+        with torch.no_grad():
+            wav = eng.decode_ragged(torch.from_numpy(codes), lengths)
+        return [wav[b: b + 1, None, : eng.hop * int(n)].detach() for b, n in enumerate(lengths)]
 
     def forward(self, audio_pathes: list):
         """distil_codec.py:518-530 (eval semantics)."""

@@ -363,6 +363,36 @@ int dcx_tokenize_ragged(dcx_codec* h, const float* audio_packed, const int32_t* 
   return tokenize_ragged_rows(h, audio_packed, g, codes, x_pjt_in, quantized_fup, ws, s);
 }
 
+// Ragged decode: the padded layout with per-clip lengths in device memory.  The checks
+// both entries share; the kernels' own limits are checked where they are launched (stage_generate).
+static int ragged_decode_pre(dcx_codec* h, const void* in, const int32_t* lengths_dev, int64_t frames_max,
+                             const float* wav) {
+  if (!in || !lengths_dev || !wav || frames_max <= 0 || frames_max > INT32_MAX / 256)
+    return fail(h, DCX_ERR_INVALID_ARG, "ragged decode: null buffer or bad frames_max");
+  if (h->split_k >= 2)
+    return fail(h, DCX_ERR_STATE, "ragged decode with split-K on: the split kernels' reduce is not length-aware");
+  if (h->gemm_mode != DCX_GEMM_X6)
+    return fail(h, DCX_ERR_INVALID_ARG, "ragged decode runs in DCX_GEMM_X6 (the other modes' kernels are not length-aware)");
+  return DCX_OK;
+}
+
+int dcx_generate_ragged(dcx_codec* h, const float* z, const int32_t* lengths_dev, int32_t batch, int64_t frames_max,
+                        float* wav, void* workspace, size_t ws_bytes, void* stream) {
+  if (h && (!z || !lengths_dev)) return fail(h, DCX_ERR_INVALID_ARG, "ragged decode: null buffer");
+  STAGE_PRE(true);
+  RUN(ragged_decode_pre(h, z, lengths_dev, frames_max, wav));
+  return stage_generate(h, CAct(z, nullptr), batch, (int)frames_max, wav, ws, s, lengths_dev);
+}
+
+int dcx_decode_ragged(dcx_codec* h, const int32_t* codes, const int32_t* lengths_dev, int32_t batch,
+                      int64_t frames_max, float* wav, int32_t* n_invalid, void* workspace, size_t ws_bytes,
+                      void* stream) {
+  if (h && (!codes || !lengths_dev)) return fail(h, DCX_ERR_INVALID_ARG, "ragged decode: null buffer");
+  STAGE_PRE(true);
+  RUN(ragged_decode_pre(h, codes, lengths_dev, frames_max, wav));
+  return stage_decode_ragged(h, codes, lengths_dev, batch, (int)frames_max, wav, n_invalid, ws, s);
+}
+
 int dcx_module_io(const dcx_codec* h, const char* module, int32_t* in_channels, int32_t* out_channels,
                   int32_t* out_rate) {
   if (!h || !module) return DCX_ERR_INVALID_ARG;

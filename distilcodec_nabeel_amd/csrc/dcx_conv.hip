@@ -1061,7 +1061,8 @@ hipError_t launch_conv_group(const ConvParams* ps, int n, int batch, hipStream_t
   for (int i = 0; i < n; ++i) {
     const ConvParams& p = ps[i];
     if (h3) {
-      if (p.Cout != cout || p.x_compact != 3 || p.taps < 3 || x3dq_bn(p) != bsel || !x3dq_ok(p, bn, bsel >= 384))
+      if (p.Cout != cout || p.x_compact != 3 || p.taps < 3 || x3dq_bn(p) != bsel || !x3dq_ok(p, bn, bsel >= 384) ||
+          (p.clip_len != nullptr) != (ps[0].clip_len != nullptr))
         return hipErrorNotSupported;
     } else if (p.Cout != cout || cout % 128 || p.Cin % BK || !p.x6 || !p.w6 || p.nprod != 6 || p.x_compact ||
                p.taps < 3 || tap_span(p) == 0 || tap_span(p) > 64 || (p.Cin / BK) * p.taps % 2 ||

@@ -238,7 +238,11 @@ __device__ __forceinline__ EpiPre epi_range_pre(const ConvParams& p, const ConvP
 // epilogues (with them, round 6's first form spilled ~290 SGPRs into VGPR lanes in
 // conv_gemm_x3dw_group: +5 % on the dominant kernel).  pr: where the range fields are read (the
 // kernel argument itself in grouped launches, whose private copy then leaves them out).
-template <int BM, int BN, int WM, int WN, int LDS_FLOATS, int NT, int RROW = 2, typename AccT>
+// RAG: whether the epilogue looks at ConvParams::clip_len (ragged batches) at all.  The h3 kernels,
+// most of a step, are instantiated both ways and launched by whether the call has lengths, so the
+// padded path runs the code it ran before the lengths existed (with the null-pointer select alone the
+// C2 step paid 0.6-1.2 %, DESIGN.md §5 "Ragged decode"); every other kernel keeps the select.
+template <int BM, int BN, int WM, int WN, int LDS_FLOATS, int NT, int RROW = 2, bool RAG = true, typename AccT>
 __device__ __forceinline__ void epilogue_lds(const ConvParams& p, const ConvParams& pr, AccT& acc, int q0, int co0,
                                              int b, int ph, float* smem, const EpiPre* pre = nullptr) {
   constexpr int WR = BM / WM, WC = BN / WN;
@@ -286,6 +290,8 @@ __device__ __forceinline__ void epilogue_lds(const ConvParams& p, const ConvPara
 #endif
   const float acur = pre ? pre->acur : track && !h2row ? range_cur(pr.y_amax, b) : 0.f;  // the clip's running max (range_report)
   float vmax = 0.f;  // largest |v| this thread finishes (range_report)
+  // ragged batch: the clip's rows that hold data; the rows from there to p.Lq are written as zeros
+  const int lq_live = RAG ? clip_rows(pr.clip_len, pr.len_mul, b, p.Lq) : p.Lq;
   // Each thread finishes G consecutive output channels of a row (G = 8: 16-byte plane / compact
   // stores; the epilogue's store issue, not its bytes, sets its pace), the same channels for every
   // row, so bias and gamma are loaded once per tile.
@@ -435,6 +441,7 @@ __device__ __forceinline__ void epilogue_lds(const ConvParams& p, const ConvPara
             break;
           default: break;
         }
+        if (RAG && q >= lq_live) x[h] = f32x4{0.f, 0.f, 0.f, 0.f};  // beyond the clip's length (its own zero padding)
       }
 #ifdef DCX_EPI_NOSTORE  // timing build: every output computed, (practically) none stored
       if (x[0][0] != -0x1.234p-100f) continue;
@@ -448,12 +455,12 @@ __device__ __forceinline__ void epilogue_lds(const ConvParams& p, const ConvPara
         continue;
       } else if (p.mean_mode == MEAN_MID) {
 #pragma unroll
-        for (int h = 0; h < NH; ++h) *reinterpret_cast<f32x4*>(p.macc + o + 4 * h) = m[k][h] + x[h];
+        for (int h = 0; h < NH; ++h) *reinterpret_cast<f32x4*>(p.macc + o + 4 * h) = RAG && q >= lq_live ? x[h] : m[k][h] + x[h];
         continue;
       } else if (p.mean_mode == MEAN_LAST) {
 #pragma unroll
         for (int h = 0; h < NH; ++h) {  // bf16 mode: stack(...).mean(0) of bf16 tensors is bf16
-          x[h] = (m[k][h] + x[h]) / 3.0f;
+          x[h] = RAG && q >= lq_live ? x[h] : (m[k][h] + x[h]) / 3.0f;
           if (p.round_bf16) x[h] = round_bf16x4(x[h]);
         }
       }
@@ -547,6 +554,60 @@ __device__ __forceinline__ void epilogue_lds(const ConvParams& p, const ConvPara
   if (track)  // workgroup-uniform; the staging area is free after the last pass
     range_report_wg(vmax, h2row ? nullptr : pr.y_amax, b, h2row ? 65504.0f : h2o ? 65504.0f / osc : __builtin_inff(),
                     pr.rflag, acur, smem, NT);
+}
+
+// Ragged batches (ConvParams::clip_len): whether the tile of clip b that starts at output row q0 lies
+// wholly beyond the clip's length.  Workgroup-uniform.  A kernel that asks before it issues any DMA
+// and before its first barrier may then leave through epilogue_dead instead of its main loop.
+__device__ __forceinline__ bool tile_dead(const ConvParams& p, const ConvParams& pr, int b, int q0) {
+  return pr.clip_len != nullptr && q0 >= clip_rows(pr.clip_len, pr.len_mul, b, p.Lq);
+}
+// The epilogue of such a tile, without accumulators: what epilogue_lds writes for rows beyond the
+// clip's length (zeros in every output and layout; MEAN_LAST's mean of zeros), the clip's h2 shift as
+// epi_range_pre stores it (the clip may have no live tile at all), nothing into y_amax.  No LDS, no
+// barrier.  Tap convs only (no per-row ranges).
+template <int BM, int BN, int NT>
+__device__ __forceinline__ void epilogue_dead(const ConvParams& p, const ConvParams& pr, int q0, int co0, int b, int ph) {
+  const long long ob = (long long)b * p.y_bstride;
+  unsigned short* y6 = p.y6 ? p.y6 + ob * (p.y_compact == 1 ? 1 : p.y_compact >= 2 ? 2 : 3) : nullptr;
+  unsigned short* y6s = p.y6s ? p.y6s + ob * (p.y6s_h2 ? 2 : 3) : nullptr;
+  const bool h2o = (y6 && p.y_compact == 3) || (y6s && p.y6s_h2);
+  if (h2o && threadIdx.x == 0) {
+    const float bnd = range_bound(pr.yb, b);
+    if (pr.y_ash) pr.y_ash[b] = h2_shift(bnd);
+    if (pr.rflag && !(bnd <= 3.0e38f)) atomicOr(pr.rflag, RANGE_NONFINITE);
+  }
+  const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
+  const float z8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  constexpr int CG = BN / 8;
+  for (int i = threadIdx.x; i < BM * CG; i += NT) {
+    const int q = q0 + i / CG, co = co0 + (i % CG) * 8;
+    if (q >= p.Lq) break;
+    const long long orow = (long long)q * p.out_mul + ph;
+    const long long o = ob + orow * p.ldy + co;
+    if (p.mean_mode == MEAN_FIRST || p.mean_mode == MEAN_MID) {
+      *reinterpret_cast<f32x4*>(p.macc + o) = z4;
+      *reinterpret_cast<f32x4*>(p.macc + o + 4) = z4;
+      continue;
+    }
+    if (p.y) {
+      *reinterpret_cast<f32x4*>(p.y + o) = z4;
+      *reinterpret_cast<f32x4*>(p.y + o + 4) = z4;
+    }
+    if (y6) {
+      if (p.y_compact == 1) store_bf16x8(y6, orow, p.Cout, co, z8);
+      else if (p.y_compact == 3) store_h2_8<false>(y6, orow, p.Cout, co, z8, 1.0f);
+      else store_planes8(y6, orow, p.Cout, co, z8);
+    }
+    if (p.y2) {
+      *reinterpret_cast<f32x4*>(p.y2 + o) = z4;
+      *reinterpret_cast<f32x4*>(p.y2 + o + 4) = z4;
+    }
+    if (y6s) {
+      if (p.y6s_h2) store_h2_8<false>(y6s, orow, p.Cout, co, z8, 1.0f);
+      else store_planes8(y6s, orow, p.Cout, co, z8);
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------------------------

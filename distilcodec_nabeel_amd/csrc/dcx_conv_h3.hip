@@ -33,7 +33,8 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 // HALO = 64: convs with a tap halo (taps >= 3), input chunks double-buffered by chunk parity;
 // HALO = 0 (conv_gemm_x3dm): one-tap convs, every step opens a chunk, so the input tiles ride the
 // weight ring's 3 slots, over a descriptor of the tile's rows only (32-bit offsets at any length).
-template <int BN, int HALO>
+// RAG: the ragged-batch instantiation (ConvParams::clip_len honoured; tap convs only)
+template <int BN, int HALO, bool RAG = false>
 __device__ __forceinline__ void x3dq_tile(const ConvParams& p, const ConvParams& pr, const int wg, const int b, const int ph) {
   constexpr int BM = 32768 / BN, WN = BN / 64, WM = 8 / WN;
   constexpr int NA = HALO ? 2 : 3;
@@ -54,6 +55,12 @@ __device__ __forceinline__ void x3dq_tile(const ConvParams& p, const ConvParams&
   const int ntiles = p.Cout / BN;
   const int mt = wg / ntiles, nt = wg - mt * ntiles;
   const int q0 = mt * BM, co0 = nt * BN;
+  // ragged batches: a tile wholly beyond its clip's length writes its zeros and leaves (workgroup-
+  // uniform; nothing has been issued and no barrier met yet)
+  if (RAG && tile_dead(p, pr, b, q0)) {
+    epilogue_dead<BM, BN, 512>(p, pr, q0, co0, b, ph);
+    return;
+  }
   const int nchunks = p.Cin / 32;
   const int taps = p.taps;
   const int nsteps = nchunks * taps;
@@ -238,18 +245,18 @@ __device__ __forceinline__ void x3dq_tile(const ConvParams& p, const ConvParams&
   for (int i = 0; i < TM; ++i)
 #pragma unroll
     for (int j = 0; j < TN; ++j) acc[i][j] *= unscale;
-  epilogue_lds<BM, BN, WM, WN, LDS_B / 4, 512, HALO == 0 ? 3 : 0>(p, pr, acc, q0, co0, b, ph, reinterpret_cast<float*>(lds), &epre);
+  epilogue_lds<BM, BN, WM, WN, LDS_B / 4, 512, HALO == 0 ? 3 : 0, RAG>(p, pr, acc, q0, co0, b, ph, reinterpret_cast<float*>(lds), &epre);
 }
 
-template <int BN, int HALO>
+template <int BN, int HALO, bool RAG = false>
 __global__ void __launch_bounds__(512, 2) conv_gemm_x3dq(const ConvParams p) {
   int wg, b, ph;
   flat_tile(((p.Lq + 32768 / BN - 1) / (32768 / BN)) * (p.Cout / BN), p.batch, wg, b, ph);
-  x3dq_tile<BN, HALO>(p, p, wg, b, ph);
+  x3dq_tile<BN, HALO, RAG>(p, p, wg, b, ph);
 }
 
 // grouped launch of up to 3 h3 convs (conv_gemm_x6dq_group's member mapping)
-template <int BN>
+template <int BN, bool RAG = false>
 __global__ void __launch_bounds__(512, 2) conv_gemm_x3dq_group(const ConvGroup g) {
   const int t = blockIdx.x;
   const int k = t >= g.start[1] ? (t >= g.start[2] ? 2 : 1) : 0;
@@ -260,7 +267,7 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_x3dq_group(const ConvGroup g
   else if (k == 1) p = g.p[1];
   else p = g.p[2];
   const ConvParams& pr = k == 0 ? g.p[0] : k == 1 ? g.p[1] : g.p[2];
-  x3dq_tile<BN, 64>(p, pr, local - b * g.tiles_per_clip[k], b, 0);
+  x3dq_tile<BN, 64, RAG>(p, pr, local - b * g.tiles_per_clip[k], b, 0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -292,7 +299,7 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_x3dq_group(const ConvGroup g
 // the end of MEM1(s + 1), before the barrier that opens MEM0(s + 1), their first reader.
 // BN = 256: 256 x 256 tiles of 64 x 128 wave tiles (Cout % 256 == 0); BN = 128: 384 x 128 tiles of
 // 48 x 128 wave tiles (the C = 128 stage: 72 MFMAs per segment against x3dq's 48).
-template <int HALO, bool SPLIT, int BN = 256>
+template <int HALO, bool SPLIT, int BN = 256, bool RAG = false>
 __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams& pr, const int wg, const int b, const int ph) {
   constexpr int BM = BN == 256 ? 256 : 384, WN = BN / 128, WM = 8 / WN;
   constexpr int WR = BM / WM, WC = 128, TM = WR / 16, TN = WC / 16;
@@ -314,6 +321,12 @@ __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams&
   const int ntiles = p.Cout / BN;
   const int mt = wg / ntiles, nt = wg - mt * ntiles;
   const int q0 = mt * BM, co0 = nt * BN;
+  // ragged batches: a tile wholly beyond its clip's length writes its zeros and leaves (workgroup-
+  // uniform; nothing has been issued and no barrier met yet)
+  if (RAG && tile_dead(p, pr, b, q0)) {
+    epilogue_dead<BM, BN, 512>(p, pr, q0, co0, b, ph);
+    return;
+  }
   const int nchunks = p.Cin / 32;
   const int taps = p.taps;
   const int nsteps = nchunks * taps;
@@ -517,18 +530,18 @@ __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams&
   for (int i = 0; i < TM; ++i)
 #pragma unroll
     for (int j = 0; j < TN; ++j) acc[i][j] *= unscale;
-  epilogue_lds<BM, BN, WM, WN, LDS_B / 4, 512, HALO == 0 ? 3 : 0>(p, pr, acc, q0, co0, b, ph, reinterpret_cast<float*>(lds), &epre);
+  epilogue_lds<BM, BN, WM, WN, LDS_B / 4, 512, HALO == 0 ? 3 : 0, RAG>(p, pr, acc, q0, co0, b, ph, reinterpret_cast<float*>(lds), &epre);
 }
 
-template <int HALO, bool SPLIT, int BN = 256>
+template <int HALO, bool SPLIT, int BN = 256, bool RAG = false>
 __global__ void __launch_bounds__(512, 2) conv_gemm_x3dw(const ConvParams p) {
   constexpr int BM = BN == 256 ? 256 : 384;
   int wg, b, ph;
   flat_tile(((p.Lq + BM - 1) / BM) * (p.Cout / BN), p.batch, wg, b, ph);
-  x3dw_tile<HALO, SPLIT, BN>(p, p, wg, b, ph);
+  x3dw_tile<HALO, SPLIT, BN, RAG>(p, p, wg, b, ph);
 }
 
-template <bool SPLIT, int BN = 256>
+template <bool SPLIT, int BN = 256, bool RAG = false>
 __global__ void __launch_bounds__(512, 2) conv_gemm_x3dw_group(const ConvGroup g) {
   const int t = blockIdx.x;
   const int k = t >= g.start[1] ? (t >= g.start[2] ? 2 : 1) : 0;
@@ -539,7 +552,7 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_x3dw_group(const ConvGroup g
   else if (k == 1) p = g.p[1];
   else p = g.p[2];
   const ConvParams& pr = k == 0 ? g.p[0] : k == 1 ? g.p[1] : g.p[2];
-  x3dw_tile<64, SPLIT, BN>(p, pr, local - b * g.tiles_per_clip[k], b, 0);
+  x3dw_tile<64, SPLIT, BN, RAG>(p, pr, local - b * g.tiles_per_clip[k], b, 0);
 }
 
 // Whether conv_gemm_x3dq<bn> (taps >= 3 with a halo) or conv_gemm_x3dm<bn> (one tap) takes an h3
@@ -566,6 +579,9 @@ bool x3dq_ok(const ConvParams& p, int bn, bool wide) {
 int x3dq_bn(const ConvParams& p) {
   const int k = p.kn ? p.kn->h3_bn : 0;
   if (p.Cout % 256) return (k == 128 && p.taps >= 3) || p.taps < 2 ? 128 : 384;
+  // (a two-tap conv, the ConvTs' phases, has no x3dq form: the knob leaves it on the 256 x 256 tiles,
+  // where a whole generator call under DCX_H3_BN used to fail its launch)
+  if (p.taps == 2) return 512;
   return k == 128 ? 128 : k == 256 ? 256 : 512;
 }
 
@@ -573,10 +589,12 @@ template <int BN>
 hipError_t launch_x3dq(const ConvParams& p, int batch, int phases, hipStream_t s, const char** kname) {
   constexpr int BM = 32768 / BN;
   if (p.taps == 1) {
+    if (p.clip_len) return hipErrorNotSupported;  // the one-tap kernels take no per-clip lengths
     if (kname) *kname = BN == 256 ? "conv_gemm_x3dm<128,256>" : "conv_gemm_x3dm<256,128>";
     return launch_flat<BM, BN>(conv_gemm_x3dq<BN, 0>, p, batch, phases, 512, s);
   }
   if (kname) *kname = BN == 256 ? "conv_gemm_x3dq<128,256,halo>" : "conv_gemm_x3dq<256,128,halo>";
+  if (p.clip_len) return launch_flat<BM, BN>(conv_gemm_x3dq<BN, 64, true>, p, batch, phases, 512, s);  // ragged batch
   return launch_flat<BM, BN>(conv_gemm_x3dq<BN, 64>, p, batch, phases, 512, s);
 }
 
@@ -586,6 +604,17 @@ template hipError_t launch_x3dq<128>(const ConvParams&, int, int, hipStream_t, c
 // bsel (x3dq_bn): 384 = the 384 x 128 tiles (the C = 128 stage), 512 = the 256 x 256 tiles
 hipError_t launch_x3dw(const ConvParams& p, int bsel, int batch, int phases, hipStream_t s, const char** kname) {
   const bool sp = knobs(p).h3_split;
+  if (p.clip_len) {  // ragged batch: the length-aware instantiations (tap convs)
+    if (p.taps == 1) return hipErrorNotSupported;
+    if (bsel == 384) {
+      if (kname) *kname = "conv_gemm_x3dw<384,128,halo>";
+      return sp ? launch_flat<384, 128>(conv_gemm_x3dw<64, true, 128, true>, p, batch, phases, 512, s)
+                : launch_flat<384, 128>(conv_gemm_x3dw<64, false, 128, true>, p, batch, phases, 512, s);
+    }
+    if (kname) *kname = "conv_gemm_x3dw<256,256,halo>";
+    return sp ? launch_flat<256, 256>(conv_gemm_x3dw<64, true, 256, true>, p, batch, phases, 512, s)
+              : launch_flat<256, 256>(conv_gemm_x3dw<64, false, 256, true>, p, batch, phases, 512, s);
+  }
   if (bsel == 384) {
     if (kname) *kname = "conv_gemm_x3dw<384,128,halo>";
     return sp ? launch_flat<384, 128>(conv_gemm_x3dw<64, true, 128>, p, batch, phases, 512, s)
@@ -603,6 +632,24 @@ hipError_t launch_x3dw(const ConvParams& p, int bsel, int batch, int phases, hip
 
 // bsel 384 / 512: conv_gemm_x3dw_group; 256 / 128: conv_gemm_x3dq_group<bsel>
 hipError_t launch_h3_group(const ConvGroup& g, int bsel, bool split, unsigned blocks, hipStream_t s, const char** kname) {
+  if (g.p[0].clip_len) {  // ragged batch (every member of a group has the lengths or none): the length-aware instantiations
+    if (bsel == 384) {
+      if (kname) *kname = "conv_gemm_x3dw_group<384,128,halo>";
+      if (split) hipLaunchKernelGGL((conv_gemm_x3dw_group<true, 128, true>), dim3(blocks), dim3(512), 0, s, g);
+      else hipLaunchKernelGGL((conv_gemm_x3dw_group<false, 128, true>), dim3(blocks), dim3(512), 0, s, g);
+    } else if (bsel == 512) {
+      if (kname) *kname = "conv_gemm_x3dw_group<256,256,halo>";
+      if (split) hipLaunchKernelGGL((conv_gemm_x3dw_group<true, 256, true>), dim3(blocks), dim3(512), 0, s, g);
+      else hipLaunchKernelGGL((conv_gemm_x3dw_group<false, 256, true>), dim3(blocks), dim3(512), 0, s, g);
+    } else if (bsel == 256) {
+      if (kname) *kname = "conv_gemm_x3dq_group<128,256,halo>";
+      hipLaunchKernelGGL((conv_gemm_x3dq_group<256, true>), dim3(blocks), dim3(512), 0, s, g);
+    } else {
+      if (kname) *kname = "conv_gemm_x3dq_group<256,128,halo>";
+      hipLaunchKernelGGL((conv_gemm_x3dq_group<128, true>), dim3(blocks), dim3(512), 0, s, g);
+    }
+    return hipGetLastError();
+  }
   if (bsel == 384) {
     if (kname) *kname = "conv_gemm_x3dw_group<384,128,halo>";
     if (split) hipLaunchKernelGGL((conv_gemm_x3dw_group<true, 128>), dim3(blocks), dim3(512), 0, s, g);

@@ -126,6 +126,9 @@ int conv_params(dcx_codec* h, const ConvW& w, const ConvCall& c, bool force_f32,
   p.y_amax = c.y_amax;
   p.yb = c.yb;
   p.rflag = h->rflag;
+  p.clip_len = c.lens;
+  p.len_mul = c.len_mul;
+  if (c.lens && (c.len_mul < 1 || !x6 || one)) return fail(h, DCX_ERR_STATE, "internal: ragged conv outside x6 mode");
   p.wc = one && h->compact ? w.wc : nullptr;
   p.kn = &h->knobs;
   // compact inputs only feed one-product GEMMs; a compact output (the RNE hi value) may also be written
@@ -239,6 +242,7 @@ int run_conv(dcx_codec* h, const ConvW& w, const ConvCall& c, hipStream_t s, boo
   ConvParams p;
   RUN(conv_params(h, w, c, force_f32, p));
   const int S = force_f32 ? 1 : split_factor(h, w, c, p);
+  if (S > 1 && c.lens) return fail(h, DCX_ERR_STATE, "internal: ragged conv in the split-K mode");
   if (S > 1) return run_conv_split(h, w, c, p, S, s);
 #ifdef DCX_DIAG_DUP
   if (const int dm = diag_dup_mode()) {
@@ -407,7 +411,7 @@ ConvCall framed(CAct x, int B, int L, int C) {
 // one-tap convs).  The scale follows from the values alone, so a tensor the fused pipeline would have
 // produced in h2 itself (a LayerNorm's row-scaled output) gets the same bits here.
 int ensure_planes(dcx_codec* h, CAct& a, long long rows, int C, Bump& ws, hipStream_t s, bool compact, bool h2,
-                  int clips) {
+                  int clips, const int* lens) {
   if (h2 && a.p && !a.h2 && a.f) a.p = nullptr;
   if (!x6_mode(h) || a.p) return DCX_OK;
   const bool rh2 = h2 && !compact;
@@ -415,10 +419,12 @@ int ensure_planes(dcx_codec* h, CAct& a, long long rows, int C, Bump& ws, hipStr
   float* am = rh2 && clips ? ws.f((size_t)clips) : nullptr;
   int* ash = rh2 ? ws.i((size_t)(clips ? clips : rows)) : nullptr;
   WS_READY(h, ws, "workspace too small");
+  // a ragged batch's tensor is bounded per clip by launch_h2_ranged alone
+  if (lens && !(rh2 && clips)) return fail(h, DCX_ERR_STATE, "internal: ragged tensor outside the ranged h2 split");
   if (rh2 && clips) {
     if (clips < 1 || rows % clips) return fail(h, DCX_ERR_STATE, "internal: ranged split of a ragged batch");
     LAUNCH(h, s, "h2_ranged", 0, 12.0 * rows * C,
-           dcx::launch_h2_ranged(a.f, nullptr, p, clips, rows / clips, C, 0, 0.f, am, ash, h->rflag, s));
+           dcx::launch_h2_ranged(a.f, nullptr, p, clips, rows / clips, C, 0, 0.f, am, ash, h->rflag, s, lens, 1));
     a.r = Rng{};
     a.r.ash = ash;
     a.r.amax = am;

@@ -104,6 +104,10 @@ int run_parallel_block(dcx_codec* h, int i, int B, int Lo, const PBlockBufs& b, 
       rp.C = Co;
       rp.rflag = h->rflag;
       rp.kn = &h->knobs;
+      rp.clip_len = b.lens;
+      rp.len_mul = b.lens ? Lo / b.frames_max : 1;
+      if (b.lens && !h3)
+        return fail(h, DCX_ERR_INVALID_ARG, "ragged decode needs the h3 pair kernel (DCX_H3_PAIRS=0 or weights without h3 form)");
       if (h3)
         for (int rb = 0; rb < c.n_res; ++rb)
           if (!rp.src_amax[rb] || (ci < 2 && !rp.dst_amax[rb]))
@@ -131,6 +135,7 @@ int run_parallel_block(dcx_codec* h, int i, int B, int Lo, const PBlockBufs& b, 
       Act src = silu_on_load ? Act{ci == 0 ? b.X : b.R[rb], nullptr} : (ci == 0 ? b.XS : b.RS[rb]);
       src.r = in1[rb];
       c1[rb] = framed(src, B, Lo, Co);
+      c1[rb].ragged(b.lens, b.frames_max);
       c1[rb].silu_in = silu_on_load;
       c1[rb].silu_to(b.Tb_in[rb]);
       w1[rb] = &h->res[i][rb][ci][0];
@@ -148,6 +153,7 @@ int run_parallel_block(dcx_codec* h, int i, int B, int Lo, const PBlockBufs& b, 
         Act tin = b.Tb_in[rb];
         tin.r = tr[rb];
         c2[rb] = framed(tin, B, Lo, Co);
+        c2[rb].ragged(b.lens, b.frames_max);
         c2[rb].epi = dcx::EPI_RES;
         c2[rb].res = ci == 0 ? b.X : b.R[rb];
         c2[rb].y = b.R[rb];
@@ -174,6 +180,7 @@ int run_parallel_block(dcx_codec* h, int i, int B, int Lo, const PBlockBufs& b, 
         Act tin = b.Tb_in[rb];
         tin.r = tr[rb];
         cc = framed(tin, B, Lo, Co);
+        cc.ragged(b.lens, b.frames_max);
         cc.epi = dcx::EPI_RES;
         cc.res = b.R[rb];
         cc.macc = b.Mx;
@@ -227,19 +234,32 @@ Act fp32_form(dcx_codec* h, const Act& a, const ConvW& consumer) {
 }
 
 // conv_post and tanh (generators.py:142-145) on x = silu(the last stage's mean) [B][L][C]
-int run_conv_post(dcx_codec* h, const float* x, float* wav, int B, int L, int C, hipStream_t s) {
+int run_conv_post(dcx_codec* h, const float* x, float* wav, int B, int L, int C, hipStream_t s, const int* lens,
+                  int len_mul) {
   const int k = h->cfg.gen_post_k;
   const bool bf = h->gemm_mode == DCX_GEMM_BF16;
   LAUNCH(h, s, "conv_post_tanh", 2.0 * B * L * C * k, 4.0 * B * L * (C + 1),
          dcx::launch_conv_post_tanh(x, h->post_w, bf ? bf16_f(bf16_rne(h->post_b)) : h->post_b, wav, B, L, C, k,
-                                    bf ? 1 : 0, s));
+                                    bf ? 1 : 0, s, lens, len_mul));
   return DCX_OK;
 }
 
-int stage_generate(dcx_codec* h, CAct z, int B, int T, float* wav, Bump& ws, hipStream_t s) {
+// Ragged batches (lens, dcx_generate_ragged): the memory layout, the workspace plan and every choice
+// of a kernel family or tile (big_tiles_pay, h3_stage, takes_h3_conv, the pair launcher's tile height)
+// follow B and T, the padded frame count, never the lengths, which only the device sees: one captured
+// graph serves any lengths, and a clip's kernels do not depend on its neighbours' lengths.  Every
+// producer writes zeros from a clip's length to the padded end (ConvParams::clip_len), so every
+// consumer reads the clip's own zero padding; z is bounded where it is split (launch_h2_ranged).
+int stage_generate(dcx_codec* h, CAct z, int B, int T, float* wav, Bump& ws, hipStream_t s, const int* lens) {
   const dcx_config& c = h->cfg;
+  if (lens && !ws.dry) {
+    if (h->gemm_mode != DCX_GEMM_X6)
+      return fail(h, DCX_ERR_INVALID_ARG, "ragged decode runs in DCX_GEMM_X6 (the other modes' kernels are not length-aware)");
+    if (z.p || !takes_h3_conv(h, h->conv_pre, T))
+      return fail(h, DCX_ERR_INVALID_ARG, "ragged decode needs conv_pre in h3 arithmetic (DCX_H3=0: z would be split unbounded)");
+  }
   // z in conv_pre's h2 form, range-scaled by each clip's exact max (the fused pipeline's z as well)
-  RUN(ensure_planes(h, z, (long long)B * T, c.vq_dim, ws, s, false, takes_h3_conv(h, h->conv_pre, T), B));
+  RUN(ensure_planes(h, z, (long long)B * T, c.vq_dim, ws, s, false, takes_h3_conv(h, h->conv_pre, T), B, lens));
   const size_t per = (size_t)B * T * max_gen_width(c);
   // The ParallelBlock's ResBlocks are independent until the mean, so each keeps its own state and
   // the convs of one dilation index run as one grouped launch (run_conv_group).
@@ -273,6 +293,7 @@ int stage_generate(dcx_codec* h, CAct z, int B, int T, float* wav, Bump& ws, hip
   int C = c.gen_channels, L = T;
   {  // conv_pre, then the first stage's SiLU (generators.py:121,125) fused as the only output
     ConvCall cc = framed(z, B, T, c.vq_dim);
+    cc.ragged(lens, T);
     Act S0 = S;
     S0.h2 = S.p && takes_h3_conv(h, h->ups[0], T);
     cc.silu_to(S0);
@@ -304,6 +325,7 @@ int stage_generate(dcx_codec* h, CAct z, int B, int T, float* wav, Bump& ws, hip
     float* amax_X = ra.amax();
     {
       ConvCall cc = framed(S_i, B, L, C);
+      cc.ragged(lens, T);
       cc.y = X;
       if (!silu_on_load) cc.silu_to(XS_i);
       cc.yb = prog_conv(up, S_i.r);
@@ -325,6 +347,8 @@ int stage_generate(dcx_codec* h, CAct z, int B, int T, float* wav, Bump& ws, hip
     pb.last = i == c.n_ups - 1;
     pb.amax_X = amax_X;
     pb.ra = &ra;
+    pb.lens = lens;
+    pb.frames_max = T;
     if (!pb.last) {
       pb.next = in_form(S, h->ups[i + 1]);
       pb.next.h2 = pb.next.p && takes_h3_conv(h, h->ups[i + 1], Lo);
@@ -337,7 +361,7 @@ int stage_generate(dcx_codec* h, CAct z, int B, int T, float* wav, Bump& ws, hip
     C = Co;
     L = Lo;
   }
-  return run_conv_post(h, Mx, wav, B, L, C, s);
+  return run_conv_post(h, Mx, wav, B, L, C, s, lens, L / T);
 }
 
 }  // namespace dcx::host

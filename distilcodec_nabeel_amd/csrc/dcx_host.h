@@ -323,6 +323,14 @@ struct ConvCall {
   dcx::RangeProg yb{};
   int* y_ash = nullptr;
   float* y_amax = nullptr;
+  // ragged batch (ConvParams::clip_len): per-clip frame counts in device memory and this conv's
+  // output rows (per phase) per frame; the launch's shape stays the padded one
+  const int* lens = nullptr;
+  int len_mul = 1;
+  void ragged(const int* l, int frames_max) {
+    lens = l;
+    len_mul = l ? Lq / frames_max : 1;
+  }
   void silu_to(const Act& a) {
     y2 = a.f;
     y6s = a.p;
@@ -380,6 +388,9 @@ struct PBlockBufs {
   float* next_amax = nullptr;
   int* next_ash = nullptr;
   RangeArena* ra = nullptr;
+  // ragged batch (stage_generate): per-clip frame counts (device) and the padded frame count
+  const int* lens = nullptr;
+  int frames_max = 0;
 };
 
 // ---- dcx_weights.cpp ----
@@ -408,7 +419,7 @@ int run_conv_group(dcx_codec* h, const ConvW* const* w, const ConvCall* c, int n
 ConvCall pointwise(CAct x, long long rows);
 ConvCall framed(CAct x, int B, int L, int C);
 int ensure_planes(dcx_codec* h, CAct& a, long long rows, int C, Bump& ws, hipStream_t s, bool compact = false,
-                  bool h2 = false, int clips = 0);
+                  bool h2 = false, int clips = 0, const int* lens = nullptr);
 int run_block(dcx_codec* h, const BlockW& bw, float* x, unsigned short* out6, int B, int T, Act ln, Act hid,
               hipStream_t s, int out6c = 0, const dcx::RaggedSeg* rg = nullptr);
 int run_ln(dcx_codec* h, const LnW& l, const float* x, Act y, long long rows, hipStream_t s, bool bf16_in = false);
@@ -427,19 +438,27 @@ int run_vq_search(dcx_codec* h, const float* P, const unsigned short* P6, int xl
                   int ntiles, int32_t* codes, hipStream_t s);
 int stage_vq_encode(dcx_codec* h, CAct feat, int B, int T, int32_t* codes, float* pin, float* fup, float* quant,
                     Bump& ws, hipStream_t s, const dcx::RaggedSeg* rg = nullptr);
+// lens (ragged batches; device, [B]): codes at or beyond a clip's length are neither read nor counted,
+// and the up block's depthwise conv sees zeros there, as the clip's own padding
 int stage_vq_decode(dcx_codec* h, const int32_t* codes, int B, int T, Act z, int32_t* n_invalid, Bump& ws,
-                    hipStream_t s);
+                    hipStream_t s, const int* lens = nullptr);
 int tokenize_ragged_rows(dcx_codec* h, const float* audio, const dcx::RaggedSeg& rg, int32_t* codes, float* pin,
                          float* fup, Bump& ws, hipStream_t s);
 int stage_encode_decode(dcx_codec* h, const float* audio, int B, int64_t n, int32_t* codes, float* wav, Bump& ws,
                         hipStream_t s);
+int stage_decode_ragged(dcx_codec* h, const int32_t* codes, const int* lens, int B, int T, float* wav,
+                        int32_t* n_invalid, Bump& ws, hipStream_t s);
 
 // ---- dcx_generator.cpp ----
 bool h3_stage(const dcx_codec* h, int i, long long rows);
 int run_parallel_block(dcx_codec* h, int i, int B, int Lo, const PBlockBufs& b, hipStream_t s);
 Act fp32_form(dcx_codec* h, const Act& a, const ConvW& consumer);
-int run_conv_post(dcx_codec* h, const float* x, float* wav, int B, int L, int C, hipStream_t s);
-int stage_generate(dcx_codec* h, CAct z, int B, int T, float* wav, Bump& ws, hipStream_t s);
+int run_conv_post(dcx_codec* h, const float* x, float* wav, int B, int L, int C, hipStream_t s,
+                  const int* lens = nullptr, int len_mul = 1);
+// lens (ragged batches; device, [B] frame counts): every kernel bounds clip b by lens[b]; the kernel
+// families, tiles and workspace plan follow B and T (the padded frame count) alone
+int stage_generate(dcx_codec* h, CAct z, int B, int T, float* wav, Bump& ws, hipStream_t s,
+                   const int* lens = nullptr);
 
 // ---- dcx_module.cpp ----
 bool module_io(const dcx_codec* h, const std::string& m, int& cin, int& cout, int& rate);

@@ -216,7 +216,23 @@ struct ConvParams {
   float* y_amax;
   RangeProg yb;
   int* rflag;
+  // ragged batch (dcx_generate_ragged): clip b holds clip_len[b] frames (device memory, clamped to the
+  // launch's padded length) of len_mul output rows q each (a ConvT: per phase).  The epilogue writes
+  // rows q >= clip_len[b] * len_mul as zeros in every output and keeps them out of y_amax, so every
+  // consumer reads the zero padding the clip sees alone; the main loop of a tile wholly beyond the
+  // length is skipped where the kernel can.  Null: every clip has Lq rows (same bits
+  // as before the field existed).  Read in place from the kernel argument, like the range fields.
+  const int* clip_len;
+  int len_mul;
 };
+
+// (device) the rows of clip b that hold data: all `full` of them, or the clip's own length in rows
+// (ConvParams::clip_len), clamped to [0, full].  Wave-uniform.
+__device__ __forceinline__ int clip_rows(const int* clip_len, int len_mul, int b, int full) {
+  if (!clip_len) return full;
+  const long long r = (long long)max(clip_len[b], 0) * len_mul;
+  return __builtin_amdgcn_readfirstlane((int)(r < full ? r : full));
+}
 
 // Independent convs issued as one launch (launch_conv_group); problem k owns logical tiles
 // [start[k], start[k + 1]), tiles_per_clip[k] per clip.
@@ -272,6 +288,11 @@ struct ResPairParams {
   float g1[kMaxGroup], bm1[kMaxGroup];
   int* rflag;
   const Knobs* kn;  // host only; null = the defaults
+  // ragged batch (ConvParams::clip_len; conv_res_pair_h3 only, launch_res_pair refuses the others):
+  // clip b holds clip_len[b] * len_mul of its L rows.  The T image is zero from there on, dst and
+  // mean_out are written as zeros there and stay out of dst_amax.  Null: L rows per clip.
+  const int* clip_len;
+  int len_mul;
 };
 
 // Launchers (all stream-ordered, no allocation).  Return hipError_t of the launch.
@@ -364,12 +385,16 @@ hipError_t launch_h2_rows(const float* x, unsigned short* y6, long long rows, in
 // rows (batch clips of L rows, C channels; amax zeroed here first), then y6 = h2 of f(x) * 2^a with
 // a = h2_shift(max(amax[b], floor)) stored to ash[b]; f = silu when silu != 0 (its |f(x)| <= |x|).
 // yf (may be null) receives f(x) in fp32.
+// clip_len (may be null; device, frames of len_mul rows): rows at or beyond clip b's length are not
+// read; they count as zeros in the max and are written as zeros
 hipError_t launch_h2_ranged(const float* x, float* yf, unsigned short* y6, int batch, long long L, int C, int silu,
-                            float floor, float* amax, int* ash, int* rflag, hipStream_t s);
+                            float floor, float* amax, int* ash, int* rflag, hipStream_t s,
+                            const int* clip_len = nullptr, int len_mul = 1);
 // n 32-bit words zeroed by a kernel (capture-safe ordering; hipMemsetAsync is not used on the path)
 hipError_t launch_zero_words(void* p, long long n, hipStream_t s);
 // amax[b] = max |x| over clip b (batch clips of L rows, C channels), amax zeroed here first
-hipError_t launch_clip_amax(const float* x, int batch, long long L, int C, float* amax, hipStream_t s);
+hipError_t launch_clip_amax(const float* x, int batch, long long L, int C, float* amax, hipStream_t s,
+                            const int* clip_len = nullptr, int len_mul = 1);
 // the CU count of the current device (cached per device, thread-safe)
 int device_cus();
 // whether conv_gemm_bf16dm takes a one-tap conv of this shape (then its input may be compact)
@@ -410,10 +435,18 @@ hipError_t launch_silu_act(const float* x, float* yf, unsigned short* y6, long l
 hipError_t launch_spec_mag(const float* spec, float* mag, unsigned short* mag6, float* loglin, long long rows, int nbins,
                            int ld_out, hipStream_t s);
 hipError_t launch_split_planes(const float* x, unsigned short* y6, long long rows, int C, int compact, hipStream_t s);
+// clip_len (may be null; device): the rows are clips of `frames` rows, and a row at or beyond its
+// clip's length is written as zeros without reading (or counting) its index
 hipError_t launch_gather_rows(const float* table, int ntable, const int32_t* idx, long long rows, int width,
-                              float* out, int32_t* n_invalid, int masked_row, hipStream_t s);
+                              float* out, int32_t* n_invalid, int masked_row, hipStream_t s,
+                              const int* clip_len = nullptr, long long frames = 0);
+// rows [r0, r1) of every clip of x [batch][L][C] set to zero, r0 = clip_len[b] * len_mul (ragged batches)
+hipError_t launch_zero_tail_rows(float* x, int batch, long long L, int C, const int* clip_len, int len_mul,
+                                 hipStream_t s);
+// clip_len (may be null; device, frames of len_mul samples): input rows at or beyond the clip's length
+// read as zeros and the samples there are written as zeros (a block wholly beyond it computes nothing)
 hipError_t launch_conv_post_tanh(const float* x, const float* w, float bias, float* out, int batch, int L, int C,
-                                 int k, int bf16, hipStream_t s);
+                                 int k, int bf16, hipStream_t s, const int* clip_len = nullptr, int len_mul = 1);
 hipError_t launch_transpose(const float* in, float* out, int batch, long long rows, long long cols, hipStream_t s);
 hipError_t launch_resample_poly(const float* x, int batch, long long n_in, long long xs, const double* h, int hlen,
                                 int up, int down, long long pre, float* y, long long n_out, long long ys,

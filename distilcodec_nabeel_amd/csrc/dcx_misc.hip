@@ -343,11 +343,14 @@ hipError_t launch_silu_act(const float* x, float* yf, unsigned short* y6, long l
 
 // launch_h2_ranged (round 6): the range of a tensor handed in by the caller, per clip (blockIdx.y):
 // the max |x| over the clip, then the h2 split of f(x) * 2^h2_shift(max(amax, floor)).
-__global__ void __launch_bounds__(256) clip_amax_kernel(const float* __restrict__ x, long long n4, float* amax) {
+// clip_len (ragged batches): only the clip's first clip_len[b] * len_mul rows (of c4 float4 each) count
+__global__ void __launch_bounds__(256) clip_amax_kernel(const float* __restrict__ x, long long n4, float* amax,
+                                                         const int* __restrict__ clip_len, int len_mul, int c4) {
   const int b = blockIdx.y;
   const f32x4* xb = reinterpret_cast<const f32x4*>(x) + (long long)b * n4;
+  const long long live4 = clip_len ? std::min<long long>(n4, (long long)max(clip_len[b], 0) * len_mul * c4) : n4;
   float m = 0.f;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < live4; i += (long long)gridDim.x * 256) {
     const f32x4 v = xb[i];
     m = fmaxf(m, fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w))));
   }
@@ -357,8 +360,10 @@ __global__ void __launch_bounds__(256) clip_amax_kernel(const float* __restrict_
 __global__ void __launch_bounds__(256) h2_ranged_kernel(const float* __restrict__ x, float* __restrict__ yf,
                                                          unsigned short* __restrict__ y6, long long L, int C, int silu,
                                                          float floor, const float* __restrict__ amax, int* ash,
-                                                         int* rflag) {
+                                                         int* rflag, const int* __restrict__ clip_len, int len_mul) {
   const int b = blockIdx.y;
+  // ragged batches: rows from the clip's length on are written as zeros and never read
+  const long long live4 = clip_len ? std::min<long long>(L, (long long)max(clip_len[b], 0) * len_mul) * C / 4 : L * C / 4;
   const float bound = fmaxf(amax[b], floor);
   const int sh = h2_shift(bound);
   const float sc = __builtin_ldexpf(1.0f, sh);
@@ -369,7 +374,7 @@ __global__ void __launch_bounds__(256) h2_ranged_kernel(const float* __restrict_
   const long long n4 = L * C / 4, base = (long long)b * L * C;
   for (long long i4 = (long long)blockIdx.x * 256 + threadIdx.x; i4 < n4; i4 += (long long)gridDim.x * 256) {
     const long long i = base + i4 * 4;
-    const f32x4 v = *reinterpret_cast<const f32x4*>(x + i);
+    const f32x4 v = i4 < live4 ? *reinterpret_cast<const f32x4*>(x + i) : f32x4{0.f, 0.f, 0.f, 0.f};
     float o[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) o[e] = silu ? v[e] * __builtin_amdgcn_rcpf(1.0f + __expf(-v[e])) : v[e];
@@ -432,26 +437,29 @@ hipError_t launch_zero_words(void* p, long long n, hipStream_t s) {
   return hipGetLastError();
 }
 
-hipError_t launch_clip_amax(const float* x, int batch, long long L, int C, float* amax, hipStream_t s) {
+hipError_t launch_clip_amax(const float* x, int batch, long long L, int C, float* amax, hipStream_t s,
+                            const int* clip_len, int len_mul) {
   if (C % 4 || L < 0 || batch < 1 || batch > 65535 || !amax) return hipErrorInvalidValue;
   hipError_t e = launch_zero_words(amax, batch, s);
   if (e != hipSuccess) return e;
   const long long n4 = L * C / 4;
   const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>((n4 + 255) / 256, std::max(1, 4096 / batch)));
-  if (n4 > 0) hipLaunchKernelGGL(clip_amax_kernel, dim3(gx, batch), dim3(256), 0, s, x, n4, amax);
+  if (n4 > 0) hipLaunchKernelGGL(clip_amax_kernel, dim3(gx, batch), dim3(256), 0, s, x, n4, amax, clip_len, len_mul, C / 4);
   return hipGetLastError();
 }
 
 hipError_t launch_h2_ranged(const float* x, float* yf, unsigned short* y6, int batch, long long L, int C, int silu,
-                            float floor, float* amax, int* ash, int* rflag, hipStream_t s) {
+                            float floor, float* amax, int* ash, int* rflag, hipStream_t s, const int* clip_len,
+                            int len_mul) {
   if (C % 32 || L < 0 || batch < 1 || batch > 65535 || !y6 || !amax || !ash) return hipErrorInvalidValue;
   hipError_t e = launch_zero_words(amax, batch, s);
   if (e != hipSuccess) return e;
   const long long n4 = L * C / 4;
   const long long nb = (n4 + 255) / 256;
   const unsigned gx = (unsigned)std::max<long long>(1, std::min<long long>(nb, std::max(1, 4096 / batch)));
-  if (n4 > 0) hipLaunchKernelGGL(clip_amax_kernel, dim3(gx, batch), dim3(256), 0, s, x, n4, amax);
-  hipLaunchKernelGGL(h2_ranged_kernel, dim3(gx, batch), dim3(256), 0, s, x, yf, y6, L, C, silu, floor, amax, ash, rflag);
+  if (n4 > 0) hipLaunchKernelGGL(clip_amax_kernel, dim3(gx, batch), dim3(256), 0, s, x, n4, amax, clip_len, len_mul, C / 4);
+  hipLaunchKernelGGL(h2_ranged_kernel, dim3(gx, batch), dim3(256), 0, s, x, yf, y6, L, C, silu, floor, amax, ash, rflag,
+                     clip_len, len_mul);
   return hipGetLastError();
 }
 
@@ -870,10 +878,15 @@ hipError_t launch_vq_pair_reduce(const VqRescoreArgs& a, hipStream_t s) {
 // and is counted.
 __global__ void __launch_bounds__(256) gather_rows_kernel(const float* __restrict__ table, int ntable,
                                                            const int32_t* __restrict__ idx, long long rows, int width,
-                                                           float* __restrict__ out, int32_t* n_invalid, int masked_row) {
+                                                           float* __restrict__ out, int32_t* n_invalid, int masked_row,
+                                                           const int* __restrict__ clip_len, long long frames) {
   const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (row >= rows) return;
+  if (clip_len && row % frames >= clip_len[row / frames]) {  // ragged batches: beyond the clip's length
+    for (int c = lane * 4; c < width; c += 256) *reinterpret_cast<f32x4*>(out + row * width + c) = f32x4{0.f, 0.f, 0.f, 0.f};
+    return;
+  }
   const int raw = idx[row];
   int i;
   if (raw == -1 && masked_row >= 0) {
@@ -892,10 +905,30 @@ __global__ void __launch_bounds__(256) gather_rows_kernel(const float* __restric
 }
 
 hipError_t launch_gather_rows(const float* table, int ntable, const int32_t* idx, long long rows, int width, float* out,
-                              int32_t* n_invalid, int masked_row, hipStream_t s) {
-  if (width % 4) return hipErrorInvalidValue;
+                              int32_t* n_invalid, int masked_row, hipStream_t s, const int* clip_len,
+                              long long frames) {
+  if (width % 4 || (clip_len && (frames < 1 || rows % frames))) return hipErrorInvalidValue;
   hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, table, ntable, idx, rows,
-                     width, out, n_invalid, masked_row);
+                     width, out, n_invalid, masked_row, clip_len, frames);
+  return hipGetLastError();
+}
+
+// launch_zero_tail_rows: one wave per row of the padded batch; rows below the clip's length are left alone
+__global__ void __launch_bounds__(256) zero_tail_rows_kernel(float* __restrict__ x, long long L, int C,
+                                                              const int* __restrict__ clip_len, int len_mul,
+                                                              long long rows) {
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long long b = row / L, q = row - b * L;
+  if (q < (long long)max(clip_len[b], 0) * len_mul) return;
+  for (int c = (threadIdx.x & 63) * 4; c < C; c += 256) *reinterpret_cast<f32x4*>(x + row * C + c) = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
+hipError_t launch_zero_tail_rows(float* x, int batch, long long L, int C, const int* clip_len, int len_mul,
+                                 hipStream_t s) {
+  const long long rows = (long long)batch * L;
+  if (!x || !clip_len || C % 4 || batch < 1 || L < 1 || len_mul < 1 || (rows + 3) / 4 > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(zero_tail_rows_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, x, L, C, clip_len, len_mul, rows);
   return hipGetLastError();
 }
 
@@ -909,7 +942,8 @@ hipError_t launch_gather_rows(const float* table, int ntable, const int32_t* idx
 // ---------------------------------------------------------------------------------------------
 template <int C>
 __global__ void __launch_bounds__(256) conv_post_tanh_kernel(const float* __restrict__ x, const float* __restrict__ w,
-                                                              float bias, float* __restrict__ out, int L, int k, int bf) {
+                                                              float bias, float* __restrict__ out, int L, int k, int bf,
+                                                              const int* __restrict__ clip_len, int len_mul) {
   constexpr int LD = C + 4;
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int pad = (k - 1) / 2;
@@ -919,11 +953,18 @@ __global__ void __launch_bounds__(256) conv_post_tanh_kernel(const float* __rest
   const int b = blockIdx.y;
   const int t0 = blockIdx.x * 256;
   const float* xb = x + (long long)b * L * C;
+  // ragged batches: the clip's own length bounds the input rows, and the samples from there to L are
+  // zeros (a block wholly beyond it leaves before the staging: workgroup-uniform, before the barrier)
+  const int Lc = clip_len ? (int)std::min<long long>(L, (long long)max(clip_len[b], 0) * len_mul) : L;
+  if (t0 >= Lc) {
+    if (t0 + (int)threadIdx.x < L) out[(long long)b * L + t0 + threadIdx.x] = 0.f;
+    return;
+  }
   for (int i = threadIdx.x; i < rows * (C / 4); i += 256) {
     const int r = i / (C / 4), c4 = i % (C / 4);
     const int t = t0 - pad + r;
     f32x4 v = {0.f, 0.f, 0.f, 0.f};
-    if (t >= 0 && t < L) v = *reinterpret_cast<const f32x4*>(xb + (long long)t * C + c4 * 4);
+    if (t >= 0 && t < Lc) v = *reinterpret_cast<const f32x4*>(xb + (long long)t * C + c4 * 4);
     if (bf) v = round_bf16x4(v);
     *reinterpret_cast<f32x4*>(tile + r * LD + c4 * 4) = v;
   }
@@ -931,6 +972,10 @@ __global__ void __launch_bounds__(256) conv_post_tanh_kernel(const float* __rest
   __syncthreads();
   const int t = t0 + threadIdx.x;
   if (t >= L) return;
+  if (t >= Lc) {
+    out[(long long)b * L + t] = 0.f;
+    return;
+  }
   float acc = 0.f;
   for (int j = 0; j < k; ++j) {
     const float* xr = tile + (threadIdx.x + j) * LD;
@@ -952,12 +997,12 @@ __global__ void __launch_bounds__(256) conv_post_tanh_kernel(const float* __rest
 }
 
 hipError_t launch_conv_post_tanh(const float* x, const float* w, float bias, float* out, int batch, int L, int C, int k,
-                                 int bf16, hipStream_t s) {
+                                 int bf16, hipStream_t s, const int* clip_len, int len_mul) {
   dim3 grid((unsigned)((L + 255) / 256), batch);
   const size_t lds = (size_t)((256 + k - 1) * (C + 4) + k * C) * sizeof(float);
   switch (C) {
-    case 32: hipLaunchKernelGGL(conv_post_tanh_kernel<32>, grid, dim3(256), lds, s, x, w, bias, out, L, k, bf16); break;
-    case 64: hipLaunchKernelGGL(conv_post_tanh_kernel<64>, grid, dim3(256), lds, s, x, w, bias, out, L, k, bf16); break;
+    case 32: hipLaunchKernelGGL(conv_post_tanh_kernel<32>, grid, dim3(256), lds, s, x, w, bias, out, L, k, bf16, clip_len, len_mul); break;
+    case 64: hipLaunchKernelGGL(conv_post_tanh_kernel<64>, grid, dim3(256), lds, s, x, w, bias, out, L, k, bf16, clip_len, len_mul); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();

@@ -366,7 +366,10 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair_g(const ResPairParams p)
 // ((chunk * 8 + piece) * NS + row) * 16, piece = plane * 4 + channel group).  Weights: the
 // ConvParams::w3 tap slices ([chunk][Cout][4][h' 8 | l' 8], scaled by 2^w3_shift per conv); the
 // accumulators are scaled back before the bias.  Schedule, tiles and hand-offs are conv_res_pair_g's.
-template <int C, bool MEAN, int RR = kRp3Rows<C>, bool RING = false>
+// RAG: the ragged-batch instantiation (ResPairParams::clip_len honoured), launched only when the call
+// has lengths: the kernels sit at the register limit, and with the length code in the one instantiation
+// the padded path spilled more (conv_res_pair_h3<32,mean,624,ring>: 64 -> 124 bytes of scratch per lane).
+template <int C, bool MEAN, int RR = kRp3Rows<C>, bool RING = false, bool RAG = false>
 __global__ void __launch_bounds__(512, 1) conv_res_pair_h3(const ResPairParams p) {
 #ifdef __HIP_DEVICE_COMPILE__  // the body is device code only (its host pass dropped the RING stubs)
   using A = RpH3;
@@ -563,6 +566,35 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair_h3(const ResPairParams p
     tl.look_ahead();
     const int b = tl.b, r0 = tl.r0;
     if constexpr (RING) tile_shifts(b, tl.nb);
+    // ragged batches: the clip's rows that hold data (a scalar load per tile).  Every producer of a
+    // state tensor writes zeros from there to L, so the S images need no bound of their own; the T
+    // image and the outputs take the clip's.
+    const int Lc = RAG ? clip_rows(p.clip_len, p.len_mul, b, L) : L;
+    if (RAG && r0 >= Lc) {
+      // A tile wholly beyond its clip's length (never without clip_len: r0 < L): its outputs are zeros
+      // and no tap is computed.  Workgroup-uniform, entered between tiles: every wave is past the
+      // barrier that closed the S-image commit, nothing reads the image, and the weight stream stands
+      // at a tile's first tap (fragments of tap 0 in registers, taps 0 and 1 in the ring or on their
+      // way), which is where the next tile, live or not, picks it up.  Only the S image in LDS is this
+      // tile's: the next tile's replaces it here, as the last member's c2 hooks would have.
+      const long long cb0 = (long long)b * p.bstride;
+      for (int i = tid; i < G::R * (C / 4); i += 512) {
+        const int q = r0 + i / (C / 4), c4 = (i % (C / 4)) * 4;
+        if (q >= L) break;
+        const long long o = cb0 + (long long)q * C + c4;
+        if constexpr (MEAN) {
+          *reinterpret_cast<f32x4*>(p.mean_out + o) = f32x4{0.f, 0.f, 0.f, 0.f};
+        } else {
+          for (int m = 0; m < nmem; ++m) *reinterpret_cast<f32x4*>(mpick(p.dst[0], p.dst[1], p.dst[2], m) + o) = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+      }
+      if (!tl.more) break;
+      rp_fill_issue_range<G, C, 0, NIT>(pf, p.src[0] + (long long)tl.nb * p.bstride, tl.nr0, L, tid);
+      rp_fill_commit<A, G>(lds, pf, tl.nr0, L, tid, __builtin_ldexpf(1.0f, RING ? shs0n : s_shift(0, tl.nb)));
+      rp_barrier();
+      tl.advance();
+      continue;
+    }
     for (int m = 0; m < nmem; ++m) {
       const int k = p.taps[m], hk = (k - 1) >> 1, d = p.dil[m];
       const long long cb0 = (long long)b * p.bstride;
@@ -579,7 +611,7 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair_h3(const ResPairParams p
       // ---- T image, range-scaled (rigorous bound: no per-element check, epilogue_lds)
       const int sh_t = RING ? mpick(sht[0], sht[1], sht[2], m) : t_shift(m, b);
       const float us1 = __builtin_ldexpf(1.0f, -(p.w3_shift1[m] + (RING ? mpick(shs[0], shs[1], shs[2], m) : s_shift(m, b))));
-      rp_t_image<A, G, C>(lds, bias_lds + m * C, acc, ln, r0, L, us1, __builtin_ldexpf(1.0f, sh_t));
+      rp_t_image<A, G, C>(lds, bias_lds + m * C, acc, ln, r0, Lc, us1, __builtin_ldexpf(1.0f, sh_t));
       rp_barrier();
       RP_T(tc);
       // ---- c2 over rows [r0, r0 + R) from the T image.  Tap 0 loads the residual rows, taps 1 and 2
@@ -622,7 +654,7 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair_h3(const ResPairParams p
       // ---- epilogue; its max |.| per clip for the next pair's S image
       const float us2 = __builtin_ldexpf(1.0f, -(p.w3_shift2[m] + sh_t));
       [[maybe_unused]] const float dmax =
-          rp_epilogue<A, G, C, MEAN>(p, bias_lds + (kMaxGroup + m) * C, acc, res, macc, ln, m, cb0, r0, nrb2, us2);
+          rp_epilogue<A, G, C, MEAN>(p, bias_lds + (kMaxGroup + m) * C, acc, res, macc, ln, m, cb0, r0, nrb2, us2, RAG ? Lc : 0x7fffffff);
       if constexpr (!MEAN) {
         if (p.dst_amax[m]) range_report(dmax, p.dst_amax[m], b, __builtin_inff(), nullptr, dcur);  // workgroup-uniform
       }
@@ -661,6 +693,7 @@ extern "C" int dcx_diag_rp(unsigned long long* out32, int reset) {
 hipError_t launch_res_pair(const ResPairParams& p, hipStream_t s, const char** kname) {
   if (p.nmem < 1 || p.nmem > kMaxGroup || p.batch < 1 || p.L < 1 || (p.C != 32 && p.C != 64))
     return hipErrorInvalidValue;
+  if (p.clip_len && (!p.h3 || p.len_mul < 1)) return hipErrorNotSupported;  // only conv_res_pair_h3 is length-aware
   for (int m = 0; m < p.nmem; ++m) {
     const int hk = (p.taps[m] - 1) / 2;
     if (p.taps[m] < 1 || p.taps[m] % 2 == 0 || hk > 8 || p.dil[m] < 1 || hk * p.dil[m] > 32 || !p.src[m] ||
@@ -711,7 +744,15 @@ hipError_t launch_res_pair(const ResPairParams& p, hipStream_t s, const char** k
   } while (0)
   bool ring_ok = kn.rp_ring != 0;  // the ring kernel reads every member's src_amax unconditionally
   for (int m = 0; m < p.nmem; ++m) ring_ok = ring_ok && p.src_amax[m];
-  if (p.h3 && ring_ok) {  // h3 weights, the LDS weight ring (round 6, default)
+  if (p.h3 && p.clip_len) {  // ragged batch: the length-aware instantiations, ring or per-wave loads
+    if (ring_ok) {
+      if (p.C == 32) DCX_RP_SIZES(conv_res_pair_h3, 32, 624, 240, 112, ",ring", , true, true);
+      else DCX_RP_SIZES(conv_res_pair_h3, 64, 240, 112, 48, ",ring", , true, true);
+    } else {
+      if (p.C == 32) DCX_RP_SIZES(conv_res_pair_h3, 32, 624, 240, 112, "", , false, true);
+      else DCX_RP_SIZES(conv_res_pair_h3, 64, 240, 112, 48, "", , false, true);
+    }
+  } else if (p.h3 && ring_ok) {  // h3 weights, the LDS weight ring (round 6, default)
     if (p.C == 32) DCX_RP_SIZES(conv_res_pair_h3, 32, 624, 240, 112, ",ring", , true);
     else DCX_RP_SIZES(conv_res_pair_h3, 64, 240, 112, 48, ",ring", , true);
   } else if (p.h3) {  // h3 weights: conv_res_pair_h3 (the barrier-free schedule at both widths)

@@ -338,11 +338,14 @@ __device__ __forceinline__ void rp_load_res(RpRow& res, const float* src, const 
 // ---- epilogue: v = state + c2 + b2 (rows past the clip end are dropped) to dst[m], or with MEAN into
 // the ParallelBlock mean, kept in macc across the members in ResBlock order (m = v0; m += v1;
 // m = (m + v2) / 3) and written as silu(mean).  Returns max |v| over what this lane stored to dst
-// (!MEAN; the h3 kernel's range report).  us: the accumulators' scale back (h3) ----
+// (!MEAN; the h3 kernel's range report).  us: the accumulators' scale back (h3).  Lc: the rows of the
+// clip that hold data (ragged batches, ResPairParams::clip_len): rows in [Lc, p.L) are written as
+// zeros, the zero padding the clip sees alone, and stay out of the max ----
 template <class A, class G, int C, bool MEAN>
 __device__ __forceinline__ float rp_epilogue(const ResPairParams& p, const float* bias2, const RpRow (&acc)[G::RB1],
                                              const RpRow (&res)[G::RB1], RpRow (&macc)[MEAN ? G::RB1 : 1],
-                                             const RpLane& ln, int m, long long cb0, int r0, int nrb2, float us = 1.0f) {
+                                             const RpLane& ln, int m, long long cb0, int r0, int nrb2, float us = 1.0f,
+                                             int Lc = 0x7fffffff) {
   const bool last_m = m + 1 == p.nmem;
   float dmax = 0.f;
 #pragma unroll
@@ -353,7 +356,8 @@ __device__ __forceinline__ float rp_epilogue(const ResPairParams& p, const float
     for (int i = 0; i < G::RB1; ++i) {
       if (i >= nrb2) break;
       const int q = r0 + (ln.wr + G::WR * i) * 16 + ln.l15;
-      const f32x4 v = res[i].c[cb] + A::pre(acc[i].c[cb], us, bias);
+      const f32x4 vf = res[i].c[cb] + A::pre(acc[i].c[cb], us, bias);
+      const f32x4 v = q < Lc ? vf : f32x4{0.f, 0.f, 0.f, 0.f};
       if constexpr (!MEAN) {
         if (q < p.L) {
           *reinterpret_cast<f32x4*>(p.dst[m] + cb0 + (long long)q * C + c0) = v;

@@ -272,13 +272,17 @@ static const unsigned short* decode_table6(const dcx_codec* h) {
 
 // The decode-table rows of M codes into zd (a conv_input: planes in x6 / bf16 mode, else fp32);
 // n_invalid: optional count of codes outside the codebook (they take the masked code's row)
-static int gather_decoded(dcx_codec* h, const int32_t* codes, long long M, Act zd, int32_t* n_invalid, hipStream_t s) {
+// lens / T (ragged batches): the rows are clips of T codes, those at or beyond lens[clip] are not read
+static int gather_decoded(dcx_codec* h, const int32_t* codes, long long M, Act zd, int32_t* n_invalid, hipStream_t s,
+                          const int* lens = nullptr, int T = 0) {
   const int D = h->cfg.vq_dim, NC = h->cfg.codebook_size;
   if (x6_mode(h))
     LAUNCH(h, s, "gather_rows", 0, 12.0 * M * D,
-           dcx::launch_gather_rows((const float*)decode_table6(h), NC, codes, M, D * 3 / 2, (float*)zd.p, n_invalid, NC, s));
+           dcx::launch_gather_rows((const float*)decode_table6(h), NC, codes, M, D * 3 / 2, (float*)zd.p, n_invalid, NC, s,
+                                   lens, T));
   else
-    LAUNCH(h, s, "gather_rows", 0, 8.0 * M * D, dcx::launch_gather_rows(h->ptable, NC, codes, M, D, zd.f, n_invalid, NC, s));
+    LAUNCH(h, s, "gather_rows", 0, 8.0 * M * D,
+           dcx::launch_gather_rows(h->ptable, NC, codes, M, D, zd.f, n_invalid, NC, s, lens, T));
   return DCX_OK;
 }
 
@@ -340,7 +344,7 @@ int stage_vq_encode(dcx_codec* h, CAct feat, int B, int T, int32_t* codes, float
 
 // z.f is required (fp32 residual stream of the up-path block); z.p optionally receives planes.
 int stage_vq_decode(dcx_codec* h, const int32_t* codes, int B, int T, Act z, int32_t* n_invalid, Bump& ws,
-                    hipStream_t s) {
+                    hipStream_t s, const int* lens) {
   const dcx_config& c = h->cfg;
   const long long M = (long long)B * T;
   const int D = c.vq_dim;
@@ -350,10 +354,15 @@ int stage_vq_decode(dcx_codec* h, const int32_t* codes, int B, int T, Act z, int
   row_ranges(h, ws, M, ln, hid);
   WS_READY(h, ws, "workspace too small for vq_decode");
   if (z.p && z.h2) return fail(h, DCX_ERR_STATE, "internal: z in h2 is split by the generator (ranged per clip)");
-  RUN(gather_decoded(h, codes, M, zd, n_invalid, s));
+  RUN(gather_decoded(h, codes, M, zd, n_invalid, s, lens, T));
   ConvCall cu = pointwise(zd, M);
   cu.y = z.f;
   RUN(run_conv(h, h->vq_up, cu, s));
+  // ragged batches: the block's depthwise conv is the one step here that reads neighbouring rows; with
+  // its input zero from each clip's length on it sees the padding the clip has alone.  The block's
+  // rows beyond the lengths are computed and never read (the generator bounds z by the same lengths).
+  if (lens)
+    LAUNCH(h, s, "zero_tail_rows", 0, 0, dcx::launch_zero_tail_rows(z.f, B, T, D, lens, 1, s));
   RUN(run_block(h, h->vq_up_blk, z.f, z.p, B, T, ln, hid, s));
   return DCX_OK;
 }
@@ -450,6 +459,22 @@ static int encode_decode_clips(dcx_codec* h, const float* audio, int B, int64_t 
   }
   if (ws.dry) ws.off = need;
   return DCX_OK;
+}
+
+// codes -> z -> waveform of a ragged batch in the padded layout (dcx_decode_ragged): z and the VQ
+// decode's scratch are a part of what encode_decode_clips carves for the same (B, T), so
+// dcx_workspace_size covers the call.  One stream: no half-batch fork.
+int stage_decode_ragged(dcx_codec* h, const int32_t* codes, const int* lens, int B, int T, float* wav,
+                        int32_t* n_invalid, Bump& ws, hipStream_t s) {
+  Act z;
+  z.f = ws.f((size_t)B * T * h->cfg.vq_dim);  // fp32 alone: the generator splits it per clip (stage_generate checks)
+  const size_t mark = ws.off;
+  Bump front(ws.base, ws.cap, ws.dry);
+  front.off = mark;
+  RUN(stage_vq_decode(h, codes, B, T, z, n_invalid, front, s, lens));
+  Bump tail(ws.base, ws.cap, ws.dry);
+  tail.off = mark;
+  return stage_generate(h, CAct(z), B, T, wav, tail, s, lens);
 }
 
 // Half-batches on two streams (Knobs::enc_streams >= 2; 1 forks inside the encoder only): clips

@@ -290,6 +290,54 @@ class NativeCodec:
                                                    ws.numel(), self._stream()))
         return codes, offsets, pin, fup
 
+    def _ragged_lengths(self, lengths, B: int, T: int) -> torch.Tensor:
+        """Per-clip frame counts for the ragged decode calls as a device int32 tensor.  A device
+        tensor is taken as it stands (a captured graph's lengths buffer; the kernels clamp to
+        [0, T]); anything else is validated on the host (ragged.check_lengths) and uploaded."""
+        if isinstance(lengths, torch.Tensor) and lengths.is_cuda:
+            if lengths.dtype != torch.int32 or lengths.numel() != B or not lengths.is_contiguous():
+                raise ValueError(f"device lengths must be contiguous int32 [{B}]")
+            return lengths
+        from .ragged import check_lengths
+        return torch.from_numpy(check_lengths(lengths, B, T)).to(self.device)
+
+    def generate_ragged(self, z: torch.Tensor, lengths, ws: torch.Tensor | None = None,
+                        wav: torch.Tensor | None = None) -> torch.Tensor:
+        """z (B, T_max, vq_dim) fp32 with per-clip frame counts `lengths` -> wav (B, 256 T_max): clip
+        b's first 256 lengths[b] samples are what the clip gives alone, the rest zeros; rows of z at
+        or beyond a length are never read (dcx_generate_ragged)."""
+        if not self.with_generator:
+            raise RuntimeError("this engine was built without generator weights")
+        z = self._dev(z, torch.float32)
+        B, T, _ = z.shape
+        lens = self._ragged_lengths(lengths, B, T)
+        if wav is None:
+            wav = torch.empty(B, self.hop * T, device=self.device)
+        ws = self.workspace(B, T, ws)
+        with torch.cuda.device(self.device):
+            self._check(self.L.dcx_generate_ragged(self.h, self._ptr(z), self._ptr(lens), B, T, self._ptr(wav), self._ptr(ws),
+                                                   ws.numel(), self._stream()))
+        return wav
+
+    def decode_ragged(self, codes: torch.Tensor, lengths, ws: torch.Tensor | None = None,
+                      wav: torch.Tensor | None = None, n_invalid: torch.Tensor | None = None) -> torch.Tensor:
+        """codes (B, T_max) int32 with per-clip frame counts `lengths` -> wav (B, 256 T_max), as
+        generate_ragged (dcx_decode_ragged).  Entries at or beyond a length are never read;
+        n_invalid (device int32 [1], optional, zeroed by the caller) counts codes outside the
+        codebook below the lengths."""
+        if not self.with_generator:
+            raise RuntimeError("this engine was built without generator weights")
+        codes = self._dev(codes, torch.int32)
+        B, T = codes.shape
+        lens = self._ragged_lengths(lengths, B, T)
+        if wav is None:
+            wav = torch.empty(B, self.hop * T, device=self.device)
+        ws = self.workspace(B, T, ws)
+        with torch.cuda.device(self.device):
+            self._check(self.L.dcx_decode_ragged(self.h, self._ptr(codes), self._ptr(lens), B, T, self._ptr(wav),
+                                                 self._ptr(n_invalid), self._ptr(ws), ws.numel(), self._stream()))
+        return wav
+
     def module_io(self, name: str) -> tuple[int, int, int]:
         """(input channels, output channels (0: int32 codes), output rows per input row) of a module."""
         ci, co, r = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()

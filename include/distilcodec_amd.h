@@ -169,6 +169,30 @@ int dcx_tokenize_ragged(dcx_codec* h, const float* audio_packed, const int32_t* 
                         int32_t batch, int64_t total_samples, int64_t total_frames, int32_t* codes, float* x_pjt_in,
                         float* quantized_fup, void* workspace, size_t ws_bytes, void* stream);
 
+/* Ragged decode: codes (or z) of clips of different lengths -> waveforms, every clip's samples what
+ * dcx_vq_decode -> dcx_generate give for that clip ALONE.  (The padded calls reproduce the reference,
+ * which pads a batch of code lists to the longest with code 0: the generator is conv-only, so there
+ * the last samples of a short clip depend on what shares its batch.)  The layout is the padded one:
+ * z [B][frames_max][vq_dim], codes [B][frames_max], wav [B][256 * frames_max]; lengths_dev is DEVICE
+ * memory, int32 [B], frames per clip, so one hipGraph captured for (batch, frames_max) serves any
+ * lengths.  The kernels clamp each length to [0, frames_max]; validate on the host before the upload.
+ *   wav[b][0 : 256 len_b)                the clip's samples;
+ *   wav[b][256 len_b : 256 frames_max)   written as 0;
+ * rows of z / entries of codes at or beyond len_b are never read into any result, whatever they hold
+ * (NaN, codes outside the codebook), *n_invalid (device int, may be NULL) counts only entries below
+ * len_b, and a clip of length 0 yields zeros.  Compute beyond a clip's length is skipped where a
+ * kernel's tile lies wholly beyond it; memory is the padded layout's, and dcx_workspace_size(h, batch,
+ * frames_max) covers both calls.  Kernel families and tiles follow (batch, frames_max) alone.
+ * Stream-ordered, allocates nothing, never synchronises, capturable, and runs on the caller's stream
+ * alone.  DCX_GEMM_X6 only: another gemm mode, or a knob setting whose launch would reach a kernel that
+ * is not length-aware (DCX_H3=0, DCX_H3_PAIRS=0), returns DCX_ERR_INVALID_ARG with the reason in
+ * dcx_last_error, never the padded result.  DCX_ERR_STATE before dcx_finalize and while split-K is on. */
+int dcx_generate_ragged(dcx_codec* h, const float* z, const int32_t* lengths_dev, int32_t batch, int64_t frames_max,
+                        float* wav, void* workspace, size_t ws_bytes, void* stream);
+int dcx_decode_ragged(dcx_codec* h, const int32_t* codes, const int32_t* lengths_dev, int32_t batch,
+                      int64_t frames_max, float* wav, int32_t* n_invalid, void* workspace, size_t ws_bytes,
+                      void* stream);
+
 /* Sample-rate conversion by up/down for input audio at another rate (replaces librosa.resample,
  * distil_codec.py:108-110 and :676, and librosa.load(sr=...) in meldataset.py:18-20).  Polyphase FIR
  * in scipy.signal.resample_poly's form: y[b][i] = sum_m h[(i + pre)*down - up*m] * x[b][m] over the
