@@ -264,7 +264,7 @@ int run_conv(dcx_codec* h, const ConvW& w, const ConvCall& c, hipStream_t s, boo
 
 // Split-K latency mode, grouped (round 4): the few-tile convs of one ResBlock dilation index (all
 // three split-eligible) as ONE conv launch whose members get K-slice counts in proportion to their
-// K (taps x chunks), within the CU count of workgroups, and ONE launch of their reduces, instead of
+// K (taps x chunks), at least two each, within the CU count of workgroups, and ONE launch of their reduces, instead of
 // two launches per conv (a C5 hop spent ~7 us per reduce launch, 107 of them).  Returns 1 when the
 // group does not qualify (the caller splits the members one by one).
 int run_conv_group_split(dcx_codec* h, const ConvW* const* w, const ConvCall* c, ConvParams* p, int n, double fl,
@@ -291,11 +291,14 @@ int run_conv_group_split(dcx_codec* h, const ConvW* const* w, const ConvCall* c,
     chunks[i] = (long long)w[i]->taps * (w[i]->cin / 16);
     // at most the handle's split_k slices per member (dcx_set_split_k), as split_factor allows
     smax[i] = (int)std::min<long long>(std::min(h->split_k, kSplitMax), (w[i]->cin / 16) / unit);
-    S[i] = chain ? 2 : 1;
+    // every member is split, as split_factor splits it alone: with dcx_set_split_k(2) the grouped and
+    // the per-conv launches then give every conv two slices, the same partial sums and the same bits
+    // (started from one slice, a tight budget left the member with the fewest chunks unsplit)
+    S[i] = 2;
     if (S[i] > smax[i]) return 1;
     total += S[i] * tiles[i];
   }
-  if (total > 256) return 1;
+  if (total > 256) return 1;  // two slices each do not fit: the caller splits the members one by one
   // K slices: repeatedly give one more slice to the member whose slices are longest, while the
   // grid stays within one workgroup per CU
   for (;;) {

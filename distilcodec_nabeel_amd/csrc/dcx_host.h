@@ -138,6 +138,7 @@ struct dcx_codec {
   // split-K latency mode (dcx_set_split_k): at most split_k K-slices per few-tile x6 conv; the
   // partial sums live in the first kSplitScratch bytes of each stage call's workspace.  split_buf
   // points there only for the duration of one stage call (CallScope), which `busy` makes exclusive.
+  // One region per call, so one stream per call: no half-batch fork in this mode (may_fork).
   int split_k = 0;
   float* split_buf = nullptr;
   // A/B and test switches, read from the environment once at dcx_create (knobs_from_env) and changed

@@ -63,10 +63,12 @@ static int stage_mel_ragged(dcx_codec* h, const float* audio, const dcx::RaggedS
 }
 
 // Whether a call may fork its half-batches onto the side stream: a handle with one, not inside a
-// half already (fork: the caller's word on that), and a caller's stream that is not being captured
-// into a hipGraph (a captured call keeps to the caller's stream, with the same bits)
+// half already (fork: the caller's word on that), not in the split-K latency mode (both halves would
+// write their partial sums to the one h->split_buf at the same time, and a half's tile counts, so its
+// slice counts and low bits, are not the whole batch's), and a caller's stream that is not being
+// captured into a hipGraph (a captured call keeps to the caller's stream, with the same bits)
 static bool may_fork(dcx_codec* h, hipStream_t s, bool fork) {
-  if (!h->side || !fork) return false;
+  if (!h->side || !fork || h->split_k >= 2) return false;
   hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
   return hipStreamIsCapturing(s, &st) == hipSuccess && st == hipStreamCaptureStatusNone;
 }
@@ -162,7 +164,8 @@ static int encode_clips(dcx_codec* h, const CAct& mel, int B, int T, Act feat, f
 // (the 1x1 convs of a C2 batch are 0.5-7 rounds of tiles over the CUs, e.g. pwconv2 at C = 768:
 // 354 tiles = 1.38 rounds), so one half's partly filled last round runs beside the other half's
 // launches.  Every kernel computes a clip's rows alone (tiles never span clips; per-row range
-// scales), so the halves give the bits of the whole batch.
+// scales), so the halves give the bits of the whole batch.  Not in the split-K latency mode, where
+// neither holds (may_fork): the batch then runs on the caller's stream.
 int stage_encode(dcx_codec* h, CAct mel, int B, int T, Act feat, Bump& ws, hipStream_t s, const dcx::RaggedSeg* rg,
                  bool fork) {
   const dcx_config& c = h->cfg;
@@ -485,7 +488,9 @@ int stage_decode_ragged(dcx_codec* h, const int32_t* codes, const int* lens, int
 // each half.  2 (default): mel -> encoder -> VQ encode -> VQ decode per half, joined, then the
 // generator on the whole batch, so the generator's long launches (the dominant kernel) run alone;
 // 3: the generator per half too.  Not in the split-K latency mode, whose partial sums share one
-// scratch region.
+// scratch region: no level forks there (may_fork refuses, so the encoder inside the one-stream plan
+// below stays on the caller's stream too), and the workspace is sized for that plan alone (the
+// test on split_k here: a dry run does not ask may_fork).
 int stage_encode_decode(dcx_codec* h, const float* audio, int B, int64_t n, int32_t* codes, float* wav, Bump& ws,
                         hipStream_t s) {
   const int mode = h->knobs.enc_streams;

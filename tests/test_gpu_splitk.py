@@ -6,6 +6,7 @@ the stated fp32 tolerances apply:
   * encoder features against the unsplit engine: relative error < 2e-5, codes equal on every frame
     whose fp64 top-2 gap exceeds 1e-4 (decisive frames);
   * a graph-captured hop on the split engine replays bit-equal to its eager run.
+Everything here runs one clip; batches of two and three clips are in tests/test_gpu_splitk_batch.py.
 """
 import numpy as np
 import pytest
