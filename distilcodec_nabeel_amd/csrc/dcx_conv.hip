@@ -34,6 +34,7 @@
 
 #include "dcx_conv_common.h"
 #include "dcx_conv_launch.h"
+#include "dcx_conv_pingpong.h"
 
 namespace dcx {
 
@@ -184,7 +185,7 @@ __global__ void __launch_bounds__(256) splitk_epilogue_kernel(const ConvParams p
 // the reduces of a grouped split-K launch in one grid (member k: blocks [start[k], start[k + 1]))
 __global__ void __launch_bounds__(256) splitk_epilogue_group_kernel(const SplitEpiGroup g) {
   const int t = blockIdx.x;
-  const int k = t >= g.start[1] ? (t >= g.start[2] ? 2 : 1) : 0;
+  const int k = member_index(g, t);
   const long long i4 = (long long)(t - g.start[k]) * 256 + threadIdx.x;
   if (i4 >= g.total4[k]) return;
   if (g.chain) {  // g.chain members, one range of blocks (member 0's), every member in order
@@ -332,12 +333,7 @@ __global__ void __launch_bounds__(256) conv_gemm_f32(const ConvParams p) {
   };
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  DCX_ZERO_ACC16(acc, TM, TN);
 
   gload(0);
   sstore(0);
@@ -453,7 +449,7 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_bf16dm(const ConvParams p) {
   }
   unsigned short* const a_dst = lds + (group * A_G + gw) * 512;
   unsigned short* const b_dst = lds + 3 * ABUF + (group * B_G + gw) * 512;
-  auto dma_step = [&](int s, int slot) {
+  auto dma_step = [&](int s, int, int slot) {  // (step, tap 0, ring slot)
 #pragma unroll
     for (int i = 0; i < A_PW; ++i) dma16(rx, a_dst + slot * ABUF + i * 2048, a_off[i] + s * a_step, 0);
 #pragma unroll
@@ -466,17 +462,14 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_bf16dm(const ConvParams p) {
   const int a_lane = (wm * WR / 16) * 1024 + kq * 256 + l15 * 16;           // bytes in an A image
   const int b_lane = 6 * ABUF + (wn * WC / 16) * 1024 + kq * 256 + l15 * 16;  // bytes, B image of slot 0
   s16x8 af[TM], bq[TN];
-  auto readF = [&](int slot) {
+  auto readF = [&](int, int, int slot) {
 #pragma unroll
     for (int i = 0; i < TM; ++i) af[i] = *reinterpret_cast<const s16x8*>(ldsb + slot * ABUF * 2 + a_lane + i * 1024);
 #pragma unroll
     for (int j = 0; j < TN; ++j) bq[j] = *reinterpret_cast<const s16x8*>(ldsb + slot * BBUF * 2 + b_lane + j * 1024);
   };
   f32x4 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   auto mfma = [&]() {
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -491,53 +484,14 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_bf16dm(const ConvParams p) {
                                                               __builtin_bit_cast(bf16x8, bq[j]), acc[i][j], 0, 0, 0);
     __builtin_amdgcn_s_setprio(0);
   };
-  auto inc3 = [](int& slot) { slot = slot == 2 ? 0 : slot + 1; };
 
-  for (int t = 0; t < 3; ++t)
-    if (t < nsteps) dma_step(t, t);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  seg_barrier();
+  // the ping-pong schedule of conv_gemm_x6dm with taps = 1: A and B of step t ride slot t % 3
+  const StepPos l3 = pingpong3_prologue(nsteps, 1, dma_step);
+  pingpong3_drain();
   DCX_TILET(tile_t1);
-#ifdef DCX_CLOCK_DIAG
-  const unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
-#endif
-  if (group == 0) {
-    readF(0);
-    int rs = 1, ws = 0;
-    for (int s = 0; s < nsteps; ++s) {
-      mfma();  // MFMA(s)
-      seg_barrier();
-      if (s + 1 < nsteps) readF(rs);  // MEM0(s): fragments of step s + 1, issue step s + 3
-      int n = 0;
-      if (s + 3 < nsteps) n = dma_step(s + 3, ws);
-      wait_dma(n);
-      seg_barrier();
-      inc3(rs);
-      inc3(ws);
-    }
-  } else {
-    int rs = 0, ws = 0;
-    for (int s = 0; s < nsteps; ++s) {
-      readF(rs);  // MEM1(s): fragments of step s, issue step s + 2 (s >= 1)
-      int n = 0;
-      if (s >= 1 && s + 2 < nsteps) n = dma_step(s + 2, ws);
-      wait_dma(n);
-      seg_barrier();
-      mfma();  // MFMA(s)
-      seg_barrier();
-      inc3(rs);
-      if (s >= 1) inc3(ws);
-      else ws = 0;
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef DCX_CLOCK_DIAG
-  if (threadIdx.x == 0) {  // steps counted in units of 1536 ideal cycles (a K32 step is 1024)
-    atomicAdd(&g_clock_diag[0], __builtin_amdgcn_s_memtime() - t0);
-    atomicAdd(&g_clock_diag[1], __builtin_amdgcn_s_memrealtime() - r0);
-    atomicAdd(&g_clock_diag[2], (unsigned long long)(nsteps * 2 / 3));
-  }
-#endif
+  DCX_CLOCK_BEGIN;
+  pingpong3_loop<false>(group, nsteps, 1, l3, dma_step, readF, mfma);
+  DCX_CLOCK_END(nsteps * 2 / 3);  // steps counted in units of 1536 ideal cycles (a K32 step is 1024)
   DCX_TILET(tile_t2);
   if constexpr (REG) {
     // lane l of block (i, j): output channels co0 + wn*WC + 16 j + 4 (l >> 4) + e of row 16 i + (l & 15)
@@ -577,20 +531,7 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_bf16dm(const ConvParams p) {
   } else {
     epilogue_lds<BM, BN, WM, WN, LDS_US / 2, 512>(p, p, acc, q0, co0, b, ph, reinterpret_cast<float*>(lds));
   }
-#ifdef DCX_TILE_DIAG
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned long long t3 = __builtin_amdgcn_s_memrealtime();
-    const unsigned int k = atomicAdd(&g_tile_cnt, 1u);
-    if (k < (unsigned)kTileDiagMax) {
-      unsigned long long* o = g_tile_diag + 6ull * k;
-      o[0] = tile_t0; o[1] = tile_t1; o[2] = tile_t2; o[3] = t3;
-      o[4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
-      o[5] = __builtin_amdgcn_s_getreg((15 << 11) | 20) | ((unsigned long long)nsteps << 16);  // + K32 steps
-    }
-  }
-#endif
+  DCX_TILE_END(nsteps);  // + K32 steps
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -698,13 +639,7 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_bf16dp(const ConvParams p) {
     for (int j = 0; j < TN; ++j) bq[j] = *reinterpret_cast<const s16x8*>(ldsb + slot * BBUF * 2 + b_lane + j * 1024);
   };
   f32x4 acc[TM][TN];
-  auto zero = [&]() {
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  };
-  zero();
+  zero_acc(acc);
   auto mfma = [&]() {  // operands swapped: a lane's accumulator holds 4 consecutive channels of a row
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -760,9 +695,8 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_bf16dp(const ConvParams p) {
         }
       }
     }
-    zero();
+    zero_acc(acc);
   };
-  auto inc3 = [](int& slot) { slot = slot == 2 ? 0 : slot + 1; };
 
   // prologue: steps 0, 1, 2 of the stream (both groups their pieces) and the GELU table, drained
   for (int t = 0; t < 3; ++t)
@@ -788,8 +722,8 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_bf16dp(const ConvParams p) {
         ++k;
       }
       seg_barrier();
-      inc3(rs);
-      inc3(ws);
+      ring_inc(rs);
+      ring_inc(ws);
     }
   } else {
     int rs = 0, ws = 0, st = 0, k = 0;
@@ -805,9 +739,8 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_bf16dp(const ConvParams p) {
       seg_barrier();
       mfma();  // MFMA(g)
       seg_barrier();
-      inc3(rs);
-      if (g >= 1) inc3(ws);
-      else ws = 0;
+      ring_inc(rs);
+      ring_inc_issue1(ws, g);
       if (++st == nsteps) {
         st = 0;
         ++k;

@@ -2,6 +2,7 @@
 // conv_gemm_x3dw, their grouped forms, tile choice and launchers.  Fragment maps: dcx_conv.hip.
 #include "dcx_conv_common.h"
 #include "dcx_conv_launch.h"
+#include "dcx_conv_pingpong.h"
 
 namespace dcx {
 
@@ -30,6 +31,18 @@ DCX_DIAG_FILE(h3)
 // ---------------------------------------------------------------------------------------------
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
+// Ragged batches: a tile wholly beyond its clip's length writes its zeros and the caller leaves
+// (workgroup-uniform; nothing has been issued and no barrier met yet, and of the tile's geometry
+// only its origin is computed before the test).
+template <int BM, int BN>
+__device__ __forceinline__ bool ragged_tile_done(const ConvParams& p, const ConvParams& pr, int wg, int b, int ph) {
+  int q0, co0;
+  tile_origin<BM, BN>(p, wg, q0, co0);
+  if (!tile_dead(p, pr, b, q0)) return false;
+  epilogue_dead<BM, BN, 512>(p, pr, q0, co0, b, ph);
+  return true;
+}
+
 // HALO = 64: convs with a tap halo (taps >= 3), input chunks double-buffered by chunk parity;
 // HALO = 0 (conv_gemm_x3dm): one-tap convs, every step opens a chunk, so the input tiles ride the
 // weight ring's 3 slots, over a descriptor of the tile's rows only (32-bit offsets at any length).
@@ -48,29 +61,13 @@ __device__ __forceinline__ void x3dq_tile(const ConvParams& p, const ConvParams&
   static_assert(LDS_B <= 160 * 1024, "LDS");
   __shared__ __attribute__((aligned(16))) unsigned short lds[LDS_B / 2];
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int group = __builtin_amdgcn_readfirstlane(tid >> 8);
-  const int gw = __builtin_amdgcn_readfirstlane((tid >> 6) & 3);
-  const int wm = wave / WN, wn = wave % WN;
-  const int ntiles = p.Cout / BN;
-  const int mt = wg / ntiles, nt = wg - mt * ntiles;
-  const int q0 = mt * BM, co0 = nt * BN;
-  // ragged batches: a tile wholly beyond its clip's length writes its zeros and leaves (workgroup-
-  // uniform; nothing has been issued and no barrier met yet)
-  if (RAG && tile_dead(p, pr, b, q0)) {
-    epilogue_dead<BM, BN, 512>(p, pr, q0, co0, b, ph);
-    return;
-  }
-  const int nchunks = p.Cin / 32;
-  const int taps = p.taps;
-  const int nsteps = nchunks * taps;
-  const int lo_rel = p.in_step < 0 ? (taps - 1) * p.in_step : 0;
-  const int row0 = q0 + p.in_base[ph] + lo_rel;
+  if constexpr (RAG)
+    if (ragged_tile_done<BM, BN>(p, pr, wg, b, ph)) return;
+  const TileGeo g = tile_geo<BM, BN, WN>(p, wg, ph, p.Cin / 32);
+  const int lane = g.lane, group = g.group, gw = g.gw, wm = g.wm, wn = g.wn, q0 = g.q0, co0 = g.co0;
+  const int nchunks = g.nchunks, taps = g.taps, nsteps = g.nsteps, lo_rel = g.lo_rel, row0 = g.row0;
   const int arow = p.ldx * 4;  // bytes per h2 row
-  const __amdgpu_buffer_rsrc_t rx =
-      HALO ? __builtin_amdgcn_make_buffer_rsrc((void*)(p.x6 + (long long)b * p.x_bstride * 2), 0, p.Lin * arow, 0x00020000)
-           : __builtin_amdgcn_make_buffer_rsrc((void*)(p.x6 + ((long long)b * p.x_bstride + (long long)row0 * p.ldx) * 2), 0,
-                                               max(0, min(BM, p.Lin - row0)) * arow, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rx = x_desc<4, HALO>(p, b, row0, BM);
   const int rbase = HALO ? row0 : 0;  // row of image row 0 relative to the descriptor
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(p.w3 + (long long)ph * taps * nchunks * p.Cout * 64), 0, taps * nchunks * p.Cout * 128, 0x00020000);
@@ -132,10 +129,7 @@ __device__ __forceinline__ void x3dq_tile(const ConvParams& p, const ConvParams&
     }
   };
   f32x4 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   // the cross terms first (hl', lh'), then hh'; 16 independent accumulators between dependent MFMAs
   // (priority 1 while issuing MFMAs: without it the C2 step took 212.0 against 192.8 ms, r05k)
   auto mfma = [&]() {
@@ -152,94 +146,16 @@ __device__ __forceinline__ void x3dq_tile(const ConvParams& p, const ConvParams&
     }
     __builtin_amdgcn_s_setprio(0);
   };
-  auto adv = [&](int& c_, int& m_) {
-    if (++m_ == taps) { m_ = 0; ++c_; }
-  };
-  auto inc3 = [](int& slot) { slot = slot == 2 ? 0 : slot + 1; };
 
-  int cl = 0, ml = 0;
-  for (int tt = 0; tt < 3; ++tt) {
-    if (tt < nsteps) dma_step(cl, ml, tt);
-    adv(cl, ml);
-  }
+  const StepPos l3 = pingpong3_prologue(nsteps, taps, dma_step);
   // the epilogue's range values and the input's unscale, in flight with the prologue's DMA
   const EpiPre epre = epi_range_pre<HALO == 0 ? 3 : 0>(p, pr, b);
   const float unscale = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int,
       __builtin_ldexpf(1.0f, -(p.w3_shift + (pr.x_ash ? pr.x_ash[b] : pr.x_ash_c))))));
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  seg_barrier();
+  pingpong3_drain();
   in_loop = true;
-  int cr = 0, mr = 0;
-#ifdef DCX_SEG_DIAG
-  unsigned long long sd[6] = {};
-#endif
-  if (group == 0) {
-    readF(0, 0, 0);
-    adv(cr, mr);
-    int rs = 1, ws = 0;  // slot of the step read next (s + 1), of the step issued next (s + 3)
-    for (int s = 0; s < nsteps; ++s) {
-      DCX_SEGT(ta);
-      mfma();  // MFMA(s)
-      DCX_SEGT(tb);
-      seg_barrier();
-      DCX_SEGT(tc);
-      // MEM0(s): issue step s + 3, fragments of step s + 1, retire step s + 2 (the DMA first: the
-      // fragment reads' latency then hides behind the DMA issue, C2 192.8 -> 190.3 ms, r05k)
-      int n = 0;
-      if (s + 3 < nsteps) n = dma_step(cl, ml, ws);
-      DCX_SEGT(tr);
-      if (s + 1 < nsteps) readF(cr, mr, rs);
-      DCX_SEGT(tq);
-      wait_dma(n);
-      DCX_SEGT(td);
-      seg_barrier();
-      DCX_SEGT(te);
-#ifdef DCX_SEG_DIAG
-      sd[0] += tb - ta; sd[1] += tc - tb; sd[2] += td - tc; sd[3] += te - td; sd[4] += tr - tc; sd[5] += tq - tr;
-#endif
-      adv(cr, mr);
-      adv(cl, ml);
-      inc3(rs);
-      inc3(ws);
-    }
-  } else {
-    int rs = 0, ws = 0;  // slot of step s, of step s + 2
-    for (int s = 0; s < nsteps; ++s) {
-      DCX_SEGT(ta);
-      // MEM1(s): issue step s + 2 (s >= 1), fragments of step s, retire step s + 1
-      int n = 0;
-      if (s >= 1 && s + 2 < nsteps) {
-        n = dma_step(cl, ml, ws);
-        adv(cl, ml);
-      }
-      DCX_SEGT(tr);
-      readF(cr, mr, rs);
-      DCX_SEGT(tq);
-      wait_dma(n);
-      DCX_SEGT(tb);
-      seg_barrier();
-      DCX_SEGT(tc);
-      mfma();  // MFMA(s)
-      DCX_SEGT(td);
-      seg_barrier();
-      DCX_SEGT(te);
-#ifdef DCX_SEG_DIAG
-      sd[2] += tb - ta; sd[3] += tc - tb; sd[0] += td - tc; sd[1] += te - td; sd[4] += tr - ta; sd[5] += tq - tr;
-#endif
-      adv(cr, mr);
-      inc3(rs);
-      if (s >= 1) inc3(ws);
-      else ws = 0;  // step 3's slot
-    }
-  }
-#ifdef DCX_SEG_DIAG
-  if ((threadIdx.x & 255) == 0) {
-#pragma unroll
-    for (int i = 0; i < 6; ++i) atomicAdd(&g_seg_diag[group * 6 + i], sd[i]);
-    if (group == 0) atomicAdd(&g_seg_diag[12], (unsigned long long)nsteps);
-  }
-#endif
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  // DMA first in the memory segments (see pingpong3_loop)
+  pingpong3_loop<true>(group, nsteps, taps, l3, dma_step, readF, mfma);
   // undo the weight and the input's range scaling (powers of two: exact)
 #pragma unroll
   for (int i = 0; i < TM; ++i)
@@ -255,19 +171,13 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_x3dq(const ConvParams p) {
   x3dq_tile<BN, HALO, RAG>(p, p, wg, b, ph);
 }
 
-// grouped launch of up to 3 h3 convs (conv_gemm_x6dq_group's member mapping)
+// grouped launch of up to 3 h3 convs (members as group_member deals them)
 template <int BN, bool RAG = false>
 __global__ void __launch_bounds__(512, 2) conv_gemm_x3dq_group(const ConvGroup g) {
-  const int t = blockIdx.x;
-  const int k = t >= g.start[1] ? (t >= g.start[2] ? 2 : 1) : 0;
-  const int local = xcd_remap(t - g.start[k], g.start[k + 1] - g.start[k]);
-  const int b = local / g.tiles_per_clip[k];
-  ConvParams p;  // a private copy of the main-loop fields (pr: the range fields, read in place by the epilogue)
-  if (k == 0) p = g.p[0];
-  else if (k == 1) p = g.p[1];
-  else p = g.p[2];
-  const ConvParams& pr = k == 0 ? g.p[0] : k == 1 ? g.p[1] : g.p[2];
-  x3dq_tile<BN, 64, RAG>(p, pr, local - b * g.tiles_per_clip[k], b, 0);
+  ConvParams p;
+  int local, b;
+  const ConvParams& pr = group_member(g, p, local, b);
+  x3dq_tile<BN, 64, RAG>(p, pr, local, b, 0);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -314,7 +224,10 @@ __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams&
   __shared__ __attribute__((aligned(16))) unsigned short lds[LDS_B / 2 + 8];  // + group 1's read counter
   unsigned int* const rd_cnt = reinterpret_cast<unsigned int*>(lds + LDS_B / 2);
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  // (its own geometry preamble, not tile_geo: with the shared one the epilogues of the 256 x 256 forms
+  // spilled 4-8 bytes more, the ragged or the padded ones depending on where the dead-tile test stood)
+  const int tid = threadIdx.x, lane = tid & 63;
+  [[maybe_unused]] const int wave = tid >> 6;
   const int group = __builtin_amdgcn_readfirstlane(tid >> 8);
   const int gw = __builtin_amdgcn_readfirstlane((tid >> 6) & 3);
   const int wm = wave / WN, wn = wave % WN;
@@ -333,10 +246,7 @@ __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams&
   const int lo_rel = p.in_step < 0 ? (taps - 1) * p.in_step : 0;
   const int row0 = q0 + p.in_base[ph] + lo_rel;
   const int arow = p.ldx * 4;  // bytes per h2 row
-  const __amdgpu_buffer_rsrc_t rx =
-      HALO ? __builtin_amdgcn_make_buffer_rsrc((void*)(p.x6 + (long long)b * p.x_bstride * 2), 0, p.Lin * arow, 0x00020000)
-           : __builtin_amdgcn_make_buffer_rsrc((void*)(p.x6 + ((long long)b * p.x_bstride + (long long)row0 * p.ldx) * 2), 0,
-                                               max(0, min(BM, p.Lin - row0)) * arow, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rx = x_desc<4, HALO>(p, b, row0, BM);
   const int rbase = HALO ? row0 : 0;  // row of image row 0 relative to the descriptor
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(p.w3 + (long long)ph * taps * nchunks * p.Cout * 64), 0, taps * nchunks * p.Cout * 128, 0x00020000);
@@ -408,10 +318,7 @@ __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams&
     }
   };
   f32x4 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   auto mfma = [&]() {
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -427,9 +334,6 @@ __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams&
     }
     __builtin_amdgcn_s_setprio(0);
   };
-  auto adv = [&](int& c_, int& m_) {
-    if (++m_ == taps) { m_ = 0; ++c_; }
-  };
 
   // prologue: steps 0 and 1, drained
   int cl = 0, ml = 0;  // the next step this group issues
@@ -437,7 +341,7 @@ __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams&
   for (int t = 0; t < 2 && t < nsteps; ++t) {
     if (group == 0) dma_step(cl, ml, t);
     else if (SPLIT) dma_step1(cl, ml, t);
-    adv(cl, ml);
+    step_adv(cl, ml, taps);
   }
   // the epilogue's range values and the input's unscale, in flight with the prologue's DMA
   const EpiPre epre = epi_range_pre<HALO == 0 ? 3 : 0>(p, pr, b);
@@ -456,7 +360,7 @@ __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams&
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       if (lane == 0) __hip_atomic_fetch_add(rd_cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     }
-    adv(cr, mr);
+    step_adv(cr, mr, taps);
     for (int s = 0; s < nsteps; ++s) {
       DCX_SEGT(ta);
       mfma();  // MFMA(s)
@@ -468,7 +372,7 @@ __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams&
       // times, r05q)
       if (s + 2 < nsteps) {
         dma_step(cl, ml, s & 1);
-        adv(cl, ml);
+        step_adv(cl, ml, taps);
       }
       DCX_SEGT(tr);
       if (s + 1 < nsteps) readF(cr, mr, (s + 1) & 1);
@@ -479,7 +383,7 @@ __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams&
 #ifdef DCX_SEG_DIAG
       sd[0] += tb - ta; sd[1] += tc - tb; sd[2] += td - tc; sd[3] += te - td; sd[4] += tr - tc; sd[5] += tq - tr;
 #endif
-      adv(cr, mr);
+      step_adv(cr, mr, taps);
     }
   } else {
     for (int s = 0; s < nsteps; ++s) {
@@ -494,7 +398,7 @@ __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams&
           while (__hip_atomic_load(rd_cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < want) {
           }
           dma_step1(cl, ml, s & 1);
-          adv(cl, ml);
+          step_adv(cl, ml, taps);
           n = B_W1;
         }
         wait_dma(n);  // step s + 1's pieces (issued in MEM1(s - 1)) landed
@@ -509,7 +413,7 @@ __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams&
 #ifdef DCX_SEG_DIAG
       sd[2] += tb - ta; sd[3] += tc - tb; sd[0] += td - tc; sd[1] += te - td; sd[5] += tb - ta;
 #endif
-      adv(cr, mr);
+      step_adv(cr, mr, taps);
     }
   }
 #ifdef DCX_SEG_DIAG
@@ -543,16 +447,10 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_x3dw(const ConvParams p) {
 
 template <bool SPLIT, int BN = 256, bool RAG = false>
 __global__ void __launch_bounds__(512, 2) conv_gemm_x3dw_group(const ConvGroup g) {
-  const int t = blockIdx.x;
-  const int k = t >= g.start[1] ? (t >= g.start[2] ? 2 : 1) : 0;
-  const int local = xcd_remap(t - g.start[k], g.start[k + 1] - g.start[k]);
-  const int b = local / g.tiles_per_clip[k];
-  ConvParams p;  // a private copy of the main-loop fields (pr: the range fields, read in place by the epilogue)
-  if (k == 0) p = g.p[0];
-  else if (k == 1) p = g.p[1];
-  else p = g.p[2];
-  const ConvParams& pr = k == 0 ? g.p[0] : k == 1 ? g.p[1] : g.p[2];
-  x3dw_tile<64, SPLIT, BN, RAG>(p, pr, local - b * g.tiles_per_clip[k], b, 0);
+  ConvParams p;
+  int local, b;
+  const ConvParams& pr = group_member(g, p, local, b);
+  x3dw_tile<64, SPLIT, BN, RAG>(p, pr, local, b, 0);
 }
 
 // Whether conv_gemm_x3dq<bn> (taps >= 3 with a halo) or conv_gemm_x3dm<bn> (one tap) takes an h3

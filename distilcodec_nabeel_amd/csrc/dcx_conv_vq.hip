@@ -3,6 +3,7 @@
 // search (launch_vq_argmin) is an instantiation of conv_gemm_f32 and stays in dcx_conv.hip.
 #include "dcx_conv_common.h"
 #include "dcx_conv_launch.h"
+#include "dcx_conv_pingpong.h"
 
 namespace dcx {
 
@@ -237,12 +238,7 @@ __global__ void __launch_bounds__(512) vq_prefilter_x3(const ConvParams p) {
   };
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  DCX_ZERO_ACC16(acc, TM, TN);
   auto mfmaSub = [&](int u) {
     __builtin_amdgcn_s_setprio(1);  // keeps the MFMA cluster together (measured +5 %)
 #pragma unroll
@@ -294,20 +290,12 @@ __global__ void __launch_bounds__(512) vq_prefilter_x3(const ConvParams p) {
   };
   // nsteps is even (launcher): no odd exit, so the loop header never merges a path with this
   // step's loads still in flight (which made the waitcnt pass drain everything, vmcnt(0))
-#ifdef DCX_CLOCK_DIAG
-  const unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
-#endif
+  DCX_CLOCK_BEGIN;
   for (int s = 0; s < nsteps; s += 2) {
     step(s, std::integral_constant<int, 0>{});
     step(s + 1, std::integral_constant<int, 1>{});
   }
-#ifdef DCX_CLOCK_DIAG
-  if (threadIdx.x == 0) {  // steps counted in units of 1536 ideal cycles (24 MFMAs x 2 waves per SIMD)
-    atomicAdd(&g_clock_diag[0], __builtin_amdgcn_s_memtime() - t0);
-    atomicAdd(&g_clock_diag[1], __builtin_amdgcn_s_memrealtime() - r0);
-    atomicAdd(&g_clock_diag[2], (unsigned long long)nsteps);
-  }
-#endif
+  DCX_CLOCK_END(nsteps);  // steps counted in units of 1536 ideal cycles (24 MFMAs x 2 waves per SIMD)
   epilogue_top2<BM, BN, WM, WN>(p, acc, q0, co0, nt, ntiles, reinterpret_cast<float*>(lds));
 }
 
@@ -373,7 +361,7 @@ __global__ void __launch_bounds__(512, 2) vq_prefilter_dm(const ConvParams p) {
   const int b_step = p.Cout * 96;
   unsigned short* const a_dst = lds + (group * G_I + gw) * 512;
   unsigned short* const b_dst = lds + 3 * ABUF + (group * G_I + gw) * 512;
-  auto dma_step = [&](int c, int slot) {
+  auto dma_step = [&](int c, int, int slot) {  // (step, tap 0, ring slot)
     const int ao = c * a_step;
     const int bo = c * b_step;
 #pragma unroll
@@ -385,7 +373,7 @@ __global__ void __launch_bounds__(512, 2) vq_prefilter_dm(const ConvParams p) {
 
   const int lrow = lane & 31, h = lane >> 5;
   s16x8 af[TM][2], bfr[TN][2];
-  auto readF = [&](int slot) {
+  auto readF = [&](int, int, int slot) {
     const unsigned short* A = lds + slot * ABUF;
     const unsigned short* Bs = lds + 3 * ABUF + slot * BBUF;
 #pragma unroll
@@ -404,12 +392,7 @@ __global__ void __launch_bounds__(512, 2) vq_prefilter_dm(const ConvParams p) {
     }
   };
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  DCX_ZERO_ACC16(acc, TM, TN);
   auto mfma = [&]() {
     __builtin_amdgcn_s_setprio(1);
 #pragma unroll
@@ -426,55 +409,13 @@ __global__ void __launch_bounds__(512, 2) vq_prefilter_dm(const ConvParams p) {
       }
     __builtin_amdgcn_s_setprio(0);
   };
-  auto inc3 = [](int& slot) { slot = slot == 2 ? 0 : slot + 1; };
 
-  // ---- prologue: steps 0, 1, 2 (both groups their pieces), drained
-  for (int t = 0; t < 3; ++t) dma_step(t, t);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  seg_barrier();
-#ifdef DCX_CLOCK_DIAG
-  const unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
-#endif
-  // Segment 2s: group 0 MFMA(s), group 1 MEM1(s); 2s + 1: group 0 MEM0(s), group 1 MFMA(s).
-  if (group == 0) {
-    readF(0);
-    int rs = 1, ws = 0;  // slot of step s + 1 (read next), of step s + 3 (issued next)
-    for (int s = 0; s < nsteps; ++s) {
-      mfma();  // MFMA(s)
-      seg_barrier();
-      // MEM0(s): fragments of step s + 1, issue step s + 3, retire step s + 2
-      if (s + 1 < nsteps) readF(rs);
-      int n = 0;
-      if (s + 3 < nsteps) n = dma_step(s + 3, ws);
-      wait_dma(n);
-      seg_barrier();
-      inc3(rs);
-      inc3(ws);
-    }
-  } else {
-    int rs = 0, ws = 0;  // slot of step s, of step s + 2
-    for (int s = 0; s < nsteps; ++s) {
-      // MEM1(s): fragments of step s, issue step s + 2 (s >= 1), retire step s + 1
-      readF(rs);
-      int n = 0;
-      if (s >= 1 && s + 2 < nsteps) n = dma_step(s + 2, ws);
-      wait_dma(n);
-      seg_barrier();
-      mfma();  // MFMA(s)
-      seg_barrier();
-      inc3(rs);
-      if (s >= 1) inc3(ws);
-      else ws = 0;  // step 3's slot
-    }
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef DCX_CLOCK_DIAG
-  if (threadIdx.x == 0) {  // steps counted in units of vq_prefilter_x3's (K32: twice these)
-    atomicAdd(&g_clock_diag[0], __builtin_amdgcn_s_memtime() - t0);
-    atomicAdd(&g_clock_diag[1], __builtin_amdgcn_s_memrealtime() - r0);
-    atomicAdd(&g_clock_diag[2], (unsigned long long)nsteps / 2);
-  }
-#endif
+  // the schedule of conv_gemm_x6dm with taps = 1 (pingpong3_loop): every step brings its own tiles
+  const StepPos l3 = pingpong3_prologue(nsteps, 1, dma_step);
+  pingpong3_drain();
+  DCX_CLOCK_BEGIN;
+  pingpong3_loop<false>(group, nsteps, 1, l3, dma_step, readF, mfma);
+  DCX_CLOCK_END(nsteps / 2);  // steps counted in units of vq_prefilter_x3's (K32: twice these)
   epilogue_top2<BM, BN, 4, WN>(p, acc, q0, co0, nt, ntiles, reinterpret_cast<float*>(lds));
 }
 
@@ -645,10 +586,7 @@ __global__ void __launch_bounds__(512, 2) vq_prefilter_b1(const ConvParams p) {
     }
   };
   f32x4 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   auto mfma = [&]() {
 #ifdef DCX_VQ_STATICPRIO  // A/B: group 1 at priority 1 throughout, no per-segment flips (MI355X_MICROARCH.md
                           // "Two waves per SIMD" item 4); the MFMA cluster fenced for the scheduler instead
@@ -668,7 +606,6 @@ __global__ void __launch_bounds__(512, 2) vq_prefilter_b1(const ConvParams p) {
     __builtin_amdgcn_s_setprio(0);
 #endif
   };
-  auto inc = [](int& slot) { slot = slot == NS - 1 ? 0 : slot + 1; };
   // pieces this wave may leave in flight at the end of a memory segment: its shares of the steps
   // after the ones the next two segments read (lo..hi inclusive, clipped to the steps that exist)
   auto in_flight = [&](int lo, int hi) { return P * max(0, min(hi, nsteps - 1) - lo + 1); };
@@ -706,8 +643,8 @@ __global__ void __launch_bounds__(512, 2) vq_prefilter_b1(const ConvParams p) {
 #ifdef DCX_SEG_DIAG
       sd[0] += tb - ta; sd[1] += tc - tb; sd[2] += td - tc; sd[3] += te - td; sd[4] += tf - te;
 #endif
-      inc(rs);
-      inc(ws);
+      ring_inc<NS>(rs);
+      ring_inc<NS>(ws);
     }
   } else {
     int rs = 0, ws = 0;
@@ -727,9 +664,8 @@ __global__ void __launch_bounds__(512, 2) vq_prefilter_b1(const ConvParams p) {
 #ifdef DCX_SEG_DIAG
       sd[0] += te - td; sd[1] += tf - te; sd[2] += tb - ta; sd[3] += tc - tb; sd[4] += td - tc;
 #endif
-      inc(rs);
-      if (s >= 1) inc(ws);
-      else ws = 0;
+      ring_inc<NS>(rs);
+      ring_inc_issue1<NS>(ws, s);
     }
   }
 #ifdef DCX_SEG_DIAG
@@ -742,20 +678,7 @@ __global__ void __launch_bounds__(512, 2) vq_prefilter_b1(const ConvParams p) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   DCX_TILET(tile_t2);
   epilogue_top2_q<BM, BN, 4, WN>(p, acc, q0, co0, nt, ntiles, reinterpret_cast<float*>(lds));
-#ifdef DCX_TILE_DIAG
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned long long t3 = __builtin_amdgcn_s_memrealtime();
-    const unsigned int k = atomicAdd(&g_tile_cnt, 1u);
-    if (k < (unsigned)kTileDiagMax) {
-      unsigned long long* o = g_tile_diag + 6ull * k;
-      o[0] = tile_t0; o[1] = tile_t1; o[2] = tile_t2; o[3] = t3;
-      o[4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
-      o[5] = __builtin_amdgcn_s_getreg((15 << 11) | 20) | ((unsigned long long)nsteps << 16);
-    }
-  }
-#endif
+  DCX_TILE_END(nsteps);
 }
 
 // ---------------------------------------------------------------------------------------------

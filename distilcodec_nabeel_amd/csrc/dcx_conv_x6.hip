@@ -3,6 +3,7 @@
 // staging), their grouped forms and launchers.  Arithmetic modes and fragment maps: dcx_conv.hip.
 #include "dcx_conv_common.h"
 #include "dcx_conv_launch.h"
+#include "dcx_conv_pingpong.h"
 
 namespace dcx {
 
@@ -34,186 +35,53 @@ __device__ __forceinline__ void x6pp_tile(const ConvParams& p, const ConvParams&
   // wave tiles 64 x (BN / 2): 24 MFMAs per segment at BN = 128
   static_assert(BN == 128 || BN == 256 || (AF32 && BN == 64), "column tile");
   constexpr int BM = AF32 ? 512 : 256, WN = AF32 ? 1 : 2, WM = 8 / WN;
-  constexpr int WR = 64, WC = BN / WN, TM = 2, TN = WC / 32;
-  constexpr int XROW = 56;  // padded 112-byte rows
-  constexpr int AROWS = BM + HALO;
-  constexpr int APC = AF32 ? 4 : 6;  // staged 16-byte pieces per input row per chunk
-  constexpr int A_P = AROWS * APC, B_P = BN * 6;        // 16-byte pieces per tile
-  constexpr int A_H = A_P / 2, B_H = B_P / 2;           // per group
-  constexpr int A_PT = (A_H + 255) / 256, B_PT = (B_H + 255) / 256;
-  constexpr int ABUF = AROWS * XROW, BBUF = BN * XROW;
-  static_assert(A_P % 2 == 0 && B_P % 2 == 0, "halves");
-  __shared__ __attribute__((aligned(16))) unsigned short lds[2 * ABUF + 2 * BBUF];
+  using S = X6Stage<BM, BN, HALO, WN, AF32>;  // the staging maps, loads / stores and fragment reads
+  constexpr int TM = S::TM, TN = S::TN;
+  __shared__ __attribute__((aligned(16))) unsigned short lds[S::LDS_US];
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int group = __builtin_amdgcn_readfirstlane(tid >> 8), gt = tid & 255;
-  const int wm = wave / WN, wn = wave % WN;
-  const int ntiles = p.Cout / BN;
-  const int mt = wg / ntiles, nt = wg - mt * ntiles;
-  const int q0 = mt * BM, co0 = nt * BN;
   int clip, c0, nchunks;
   ksplit_slice(p, b, clip, c0, nchunks);  // split-K slice (AF32 launches never split)
-  const unsigned short* __restrict__ xb6 = AF32 ? nullptr : p.x6 + (long long)clip * p.x_bstride * 3 + c0 * 48;
-  const float* __restrict__ xbf = AF32 ? p.x + (long long)clip * p.x_bstride : nullptr;
-  const long long ldx6 = (long long)p.ldx * 3;
-  const int wchunks = p.Cin / BK;  // weight layout
-  const int taps = p.taps;
-  const int nsteps = nchunks * taps;
-  const int lo_rel = p.in_step < 0 ? (taps - 1) * p.in_step : 0;
-  const int row0 = q0 + p.in_base[ph] + lo_rel;
-  const unsigned short* __restrict__ wbase =
-      p.w6 + ((long long)ph * taps * wchunks + c0) * p.Cout * 48 + (long long)co0 * 48;
-  const long long wslab = (long long)p.Cout * 48;
-  const int lin = p.Lin;
-
-  // this thread's staging slots in its group's half of each tile (surplus slots repeat the last)
-  int a_row[A_PT], a_k[A_PT], b_off[B_PT], b_lds[B_PT];
-#pragma unroll
-  for (int i = 0; i < A_PT; ++i) {
-    const int idx = group * A_H + min(gt + 256 * i, A_H - 1);
-    a_row[i] = idx / APC;
-    a_k[i] = idx - a_row[i] * APC;  // AF32: 4-channel group
-  }
-#pragma unroll
-  for (int i = 0; i < B_PT; ++i) {
-    const int idx = group * B_H + min(gt + 256 * i, B_H - 1);
-    const int col = idx / 6, piece = idx - col * 6;
-    b_off[i] = idx * 8;
-    b_lds[i] = col * XROW + piece * 8;
-  }
-  f32x4 ra[A_PT], rb[B_PT];
-  auto loadA = [&](int c) {
-#pragma unroll
-    for (int i = 0; i < A_PT; ++i) {
-      const int ir = row0 + a_row[i];
-      const bool ok = ir >= 0 && ir < lin;
-      if constexpr (AF32) {
-        const float* src = ok ? xbf + (long long)ir * p.ldx + c * 16 + a_k[i] * 4 : g_zero_row;
-        ra[i] = *reinterpret_cast<const f32x4*>(src);
-      } else {
-        const unsigned short* src =
-            ok ? xb6 + (long long)ir * ldx6 + c * 48 + a_k[i] * 8 : reinterpret_cast<const unsigned short*>(g_zero_row);
-        ra[i] = *reinterpret_cast<const f32x4*>(src);
-      }
-    }
-  };
-  auto storeA = [&](int buf) {
-#pragma unroll
-    for (int i = 0; i < A_PT; ++i) {
-      if constexpr (AF32) {  // silu (optional) and the 3-plane split of 4 channels: three 8-byte stores
-        s16x4 hv, mv, lv;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          unsigned short hb, mb, lb;
-          split3(p.silu_in ? silu_f(ra[i][e]) : ra[i][e], hb, mb, lb);  // silu(0) = 0: padding stays 0
-          hv[e] = (short)hb;
-          mv[e] = (short)mb;
-          lv[e] = (short)lb;
-        }
-        unsigned short* d = lds + buf * ABUF + a_row[i] * XROW + (a_k[i] >> 1) * 24 + (a_k[i] & 1) * 4;
-        *reinterpret_cast<s16x4*>(d) = hv;
-        *reinterpret_cast<s16x4*>(d + 8) = mv;
-        *reinterpret_cast<s16x4*>(d + 16) = lv;
-      } else {
-        *reinterpret_cast<f32x4*>(lds + buf * ABUF + a_row[i] * XROW + a_k[i] * 8) = ra[i];
-      }
-    }
-  };
-  auto loadB = [&](int c, int m) {
-    const unsigned short* src = wbase + ((long long)m * wchunks + c) * wslab;
-#pragma unroll
-    for (int i = 0; i < B_PT; ++i) rb[i] = *reinterpret_cast<const f32x4*>(src + b_off[i]);
-  };
-  auto storeB = [&](int slot) {
-#pragma unroll
-    for (int i = 0; i < B_PT; ++i) *reinterpret_cast<f32x4*>(lds + 2 * ABUF + slot * BBUF + b_lds[i]) = rb[i];
-  };
-
-  const int lrow = lane & 31, hoff = (lane >> 5) * 24;
+  const TileGeo g = tile_geo<BM, BN, WN>(p, wg, ph, nchunks);
+  const int group = g.group, taps = g.taps, nsteps = g.nsteps;
+  const S st(p, lds, g, clip, c0, ph);
+  f32x4 ra[S::A_PT], rb[S::B_PT];  // one staging register set
   s16x8 af[TM][3], bfr[TN][3];
-  auto readF = [&](int c, int m, int slot) {
-    const int off = m * p.in_step - lo_rel;
-    const unsigned short* A = lds + (c & 1) * ABUF;
-    const unsigned short* Bsm = lds + 2 * ABUF + slot * BBUF;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const unsigned short* ap = A + (wm * WR + i * 32 + lrow + off) * XROW + hoff;
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) af[i][pl] = *reinterpret_cast<const s16x8*>(ap + pl * 8);
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const unsigned short* bp = Bsm + (wn * WC + j * 32 + lrow) * XROW + hoff;
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) bfr[j][pl] = *reinterpret_cast<const s16x8*>(bp + pl * 8);
-    }
-  };
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  // s_setprio around the cluster keeps hipcc from moving MFMAs across the segment barriers
-  // (cdna_hip_programming.md T5), which would collapse the ping-pong
-  auto mfma = [&]() {
-    __builtin_amdgcn_s_setprio(1);
-#define DCX_MF(i, j, x, y) \
-  acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af[i][x]), \
-                                                      __builtin_bit_cast(bf16x8, bfr[j][y]), acc[i][j], 0, 0, 0)
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        DCX_MF(i, j, 2, 0);
-        DCX_MF(i, j, 1, 1);
-        DCX_MF(i, j, 0, 2);
-        DCX_MF(i, j, 1, 0);
-        DCX_MF(i, j, 0, 1);
-        DCX_MF(i, j, 0, 0);
-      }
-#undef DCX_MF
-    __builtin_amdgcn_s_setprio(0);
-  };
-  auto adv = [&](int& c_, int& m_) {
-    if (++m_ == taps) { m_ = 0; ++c_; }
-  };
+  DCX_ZERO_ACC16(acc, TM, TN);
+  auto mfma = [&]() { x6_mfma_segment(acc, af, bfr); };
 
   // ---- prologue: both groups stage their halves of A(0), B(0), B(1); A(1) when step 1 opens it
-  loadA(0);
-  loadB(0, 0);
-  storeA(0);
-  storeB(0);
+  st.loadA(0, ra);
+  st.loadB(0, 0, rb);
+  st.storeA(0, ra);
+  st.storeB(0, rb);
   int c1 = 0, m1 = 0;  // position of step 1
-  adv(c1, m1);
-  loadB(c1, m1);
-  storeB(1);
+  step_adv(c1, m1, taps);
+  st.loadB(c1, m1, rb);
+  st.storeB(1, rb);
   if (m1 == 0) {  // taps == 1
-    loadA(1);
-    storeA(1);
+    st.loadA(1, ra);
+    st.storeA(1, ra);
   }
   // position of the step this group stores next (group 0: step 2 in MEM0(0); group 1: step 2 in
   // MEM1(1)) and of the step it reads next; both groups start their loads for step 2
   int cw = c1, mw = m1;
-  adv(cw, mw);                        // step 2
+  step_adv(cw, mw, taps);             // step 2
   int cl = cw, ml = mw;               // next load: step 2
   if (nsteps > 2) {
-    loadB(cl, ml);
-    if (ml == 0) loadA(cl);
+    st.loadB(cl, ml, rb);
+    if (ml == 0) st.loadA(cl, ra);
   }
-  adv(cl, ml);                        // step 3
+  step_adv(cl, ml, taps);             // step 3
   __syncthreads();
-#ifdef DCX_CLOCK_DIAG
-  const unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
-#endif
+  DCX_CLOCK_BEGIN;
   int cr = 0, mr = 0;                 // position of the step whose fragments are read next
 #ifdef DCX_SEG_DIAG
   unsigned long long sd[6] = {}, tprev = 0;
 #endif
   if (group == 0) {
-    readF(0, 0, 0);
-    adv(cr, mr);                      // group 0 reads step 1 in MEM0(0)
+    st.readF(0, 0, 0, af, bfr);
+    step_adv(cr, mr, taps);           // group 0 reads step 1 in MEM0(0)
     for (int s = 0; s < nsteps; ++s) {
       DCX_SEGT(ta);
 #ifdef DCX_SEG_DIAG
@@ -225,20 +93,20 @@ __device__ __forceinline__ void x6pp_tile(const ConvParams& p, const ConvParams&
       DCX_SEGT(tc);
       // MEM0(s): fragments of step s+1, store step s+2, load step s+3 (issuing the loads before
       // the fragment reads was slower: 2480 vs 2048 cycles per step at k11)
-      if (s + 1 < nsteps) readF(cr, mr, (s + 1) & 1);
+      if (s + 1 < nsteps) st.readF(cr, mr, (s + 1) & 1, af, bfr);
       DCX_SEGT(tc1);
       if (s + 2 < nsteps) {
-        storeB((s + 2) & 1);
-        if (mw == 0) storeA(cw & 1);
+        st.storeB((s + 2) & 1, rb);
+        if (mw == 0) st.storeA(cw & 1, ra);
       }
       DCX_SEGT(tc2);
       if (s + 3 < nsteps) {
-        loadB(cl, ml);
-        if (ml == 0) loadA(cl);
+        st.loadB(cl, ml, rb);
+        if (ml == 0) st.loadA(cl, ra);
       }
-      adv(cr, mr);
-      adv(cw, mw);
-      adv(cl, ml);
+      step_adv(cr, mr, taps);
+      step_adv(cw, mw, taps);
+      step_adv(cl, ml, taps);
       DCX_SEGT(td);
       __syncthreads();
 #ifdef DCX_SEG_DIAG
@@ -258,20 +126,20 @@ __device__ __forceinline__ void x6pp_tile(const ConvParams& p, const ConvParams&
 #ifdef DCX_SEG_DIAG
       if (s) sd[1] += ta - tprev;
 #endif
-      readF(cr, mr, s & 1);
+      st.readF(cr, mr, s & 1, af, bfr);
       DCX_SEGT(ta1);
       if (s >= 1 && s + 1 < nsteps) {
-        storeB((s + 1) & 1);
-        if (mw == 0) storeA(cw & 1);
-        adv(cw, mw);
+        st.storeB((s + 1) & 1, rb);
+        if (mw == 0) st.storeA(cw & 1, ra);
+        step_adv(cw, mw, taps);
       }
       DCX_SEGT(ta2);
       if (s >= 1 && s + 2 < nsteps) {
-        loadB(cl, ml);
-        if (ml == 0) loadA(cl);
-        adv(cl, ml);
+        st.loadB(cl, ml, rb);
+        if (ml == 0) st.loadA(cl, ra);
+        step_adv(cl, ml, taps);
       }
-      adv(cr, mr);
+      step_adv(cr, mr, taps);
       DCX_SEGT(tb);
       __syncthreads();
       DCX_SEGT(tc);
@@ -296,14 +164,8 @@ __device__ __forceinline__ void x6pp_tile(const ConvParams& p, const ConvParams&
     if (group == 0) atomicAdd(&g_seg_diag[12], (unsigned long long)nsteps);
   }
 #endif
-#ifdef DCX_CLOCK_DIAG
-  if (threadIdx.x == 0) {
-    atomicAdd(&g_clock_diag[0], __builtin_amdgcn_s_memtime() - t0);
-    atomicAdd(&g_clock_diag[1], __builtin_amdgcn_s_memrealtime() - r0);
-    atomicAdd(&g_clock_diag[2], (unsigned long long)nsteps);
-  }
-#endif
-  epilogue_lds<BM, BN, WM, WN, (2 * ABUF + 2 * BBUF) / 2, 512, HALO ? 0 : 2>(p, pr, acc, q0, co0, b, ph, reinterpret_cast<float*>(lds));
+  DCX_CLOCK_END(nsteps);
+  epilogue_lds<BM, BN, WM, WN, S::LDS_US / 2, 512, HALO ? 0 : 2>(p, pr, acc, g.q0, g.co0, b, ph, reinterpret_cast<float*>(lds));
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -323,103 +185,21 @@ __device__ __forceinline__ void x6pp_tile(const ConvParams& p, const ConvParams&
 template <int HALO>
 __global__ void __launch_bounds__(512, 2) conv_gemm_x6lm(const ConvParams p) {
   constexpr int BM = 256, BN = 128, WN = 2;
-  constexpr int WR = 64, WC = BN / WN, TM = 2, TN = WC / 32;
-  constexpr int XROW = 56;  // padded 112-byte rows
-  constexpr int AROWS = BM + HALO;
-  constexpr int A_P = AROWS * 6, B_P = BN * 6;
-  constexpr int A_H = A_P / 2, B_H = B_P / 2;
-  constexpr int A_PT = (A_H + 255) / 256, B_PT = (B_H + 255) / 256;
-  constexpr int ABUF = AROWS * XROW, BBUF = BN * XROW;
-  __shared__ __attribute__((aligned(16))) unsigned short lds[2 * ABUF + 2 * BBUF];
+  using S = X6Stage<BM, BN, HALO, WN, false>;
+  constexpr int TM = S::TM, TN = S::TN, A_PT = S::A_PT, B_PT = S::B_PT;
+  __shared__ __attribute__((aligned(16))) unsigned short lds[S::LDS_US];
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int group = __builtin_amdgcn_readfirstlane(tid >> 8), gt = tid & 255;
-  const int wm = wave / WN, wn = wave % WN;
-  const int ntiles = p.Cout / BN;
   int wg, b, ph;
-  flat_tile(((p.Lq + BM - 1) / BM) * ntiles, p.batch, wg, b, ph);
-  const int mt = wg / ntiles, nt = wg - mt * ntiles;
-  const int q0 = mt * BM, co0 = nt * BN;
+  flat_tile(((p.Lq + BM - 1) / BM) * (p.Cout / BN), p.batch, wg, b, ph);
   int clip, c0, nchunks;
   ksplit_slice(p, b, clip, c0, nchunks);  // split-K slice
-  const unsigned short* __restrict__ xb6 = p.x6 + (long long)clip * p.x_bstride * 3 + c0 * 48;
-  const long long ldx6 = (long long)p.ldx * 3;
-  const int wchunks = p.Cin / BK;  // weight layout
-  const int taps = p.taps;
-  const int nsteps = nchunks * taps;
-  const int lo_rel = p.in_step < 0 ? (taps - 1) * p.in_step : 0;
-  const int row0 = q0 + p.in_base[ph] + lo_rel;
-  const unsigned short* __restrict__ wbase =
-      p.w6 + ((long long)ph * taps * wchunks + c0) * p.Cout * 48 + (long long)co0 * 48;
-  const long long wslab = (long long)p.Cout * 48;
-  const int lin = p.Lin;
-
-  int a_row[A_PT], a_k[A_PT], b_off[B_PT], b_lds[B_PT];
-#pragma unroll
-  for (int i = 0; i < A_PT; ++i) {
-    const int idx = group * A_H + min(gt + 256 * i, A_H - 1);
-    a_row[i] = idx / 6;
-    a_k[i] = idx - a_row[i] * 6;
-  }
-#pragma unroll
-  for (int i = 0; i < B_PT; ++i) {
-    const int idx = group * B_H + min(gt + 256 * i, B_H - 1);
-    const int col = idx / 6, piece = idx - col * 6;
-    b_off[i] = idx * 8;
-    b_lds[i] = col * XROW + piece * 8;
-  }
-  f32x4 ra[2][A_PT], rb[2][B_PT];
-  auto loadA = [&](int c, f32x4(&r)[A_PT]) {
-#pragma unroll
-    for (int i = 0; i < A_PT; ++i) {
-      const int ir = row0 + a_row[i];
-      const bool ok = ir >= 0 && ir < lin;
-      const unsigned short* src =
-          ok ? xb6 + (long long)ir * ldx6 + c * 48 + a_k[i] * 8 : reinterpret_cast<const unsigned short*>(g_zero_row);
-      r[i] = *reinterpret_cast<const f32x4*>(src);
-    }
-  };
-  auto storeA = [&](int buf, const f32x4(&r)[A_PT]) {
-#pragma unroll
-    for (int i = 0; i < A_PT; ++i)
-      *reinterpret_cast<f32x4*>(lds + buf * ABUF + a_row[i] * XROW + a_k[i] * 8) = r[i];
-  };
-  auto loadB = [&](int c, int m, f32x4(&r)[B_PT]) {
-    const unsigned short* src = wbase + ((long long)m * wchunks + c) * wslab;
-#pragma unroll
-    for (int i = 0; i < B_PT; ++i) r[i] = *reinterpret_cast<const f32x4*>(src + b_off[i]);
-  };
-  auto storeB = [&](int slot, const f32x4(&r)[B_PT]) {
-#pragma unroll
-    for (int i = 0; i < B_PT; ++i) *reinterpret_cast<f32x4*>(lds + 2 * ABUF + slot * BBUF + b_lds[i]) = r[i];
-  };
-
-  const int lrow = lane & 31, hoff = (lane >> 5) * 24;
+  const TileGeo g = tile_geo<BM, BN, WN>(p, wg, ph, nchunks);
+  const int group = g.group, taps = g.taps, nsteps = g.nsteps;
+  const S st(p, lds, g, clip, c0, ph);
+  f32x4 ra[2][A_PT], rb[2][B_PT];  // two staging register sets
   s16x8 af[TM][3], bfr[TN][3];
-  auto readF = [&](int c, int m, int slot) {
-    const int off = m * p.in_step - lo_rel;
-    const unsigned short* A = lds + (c & 1) * ABUF;
-    const unsigned short* Bsm = lds + 2 * ABUF + slot * BBUF;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const unsigned short* ap = A + (wm * WR + i * 32 + lrow + off) * XROW + hoff;
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) af[i][pl] = *reinterpret_cast<const s16x8*>(ap + pl * 8);
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const unsigned short* bp = Bsm + (wn * WC + j * 32 + lrow) * XROW + hoff;
-#pragma unroll
-      for (int pl = 0; pl < 3; ++pl) bfr[j][pl] = *reinterpret_cast<const s16x8*>(bp + pl * 8);
-    }
-  };
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  DCX_ZERO_ACC16(acc, TM, TN);
   // MFMA cluster of one step with the staging loads `ld` spread through it: NL loads, one after
   // every 24 / (NL + 1) MFMAs (sched_group_barrier pins the order), so their issue overlaps MFMAs
   // instead of holding back the first one
@@ -427,21 +207,7 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_x6lm(const ConvParams p) {
     constexpr int NL = decltype(nl_tag)::value;
     __builtin_amdgcn_s_setprio(1);
     ld();
-#define DCX_MF(i, j, x, y) \
-  acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af[i][x]), \
-                                                      __builtin_bit_cast(bf16x8, bfr[j][y]), acc[i][j], 0, 0, 0)
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        DCX_MF(i, j, 2, 0);
-        DCX_MF(i, j, 1, 1);
-        DCX_MF(i, j, 0, 2);
-        DCX_MF(i, j, 1, 0);
-        DCX_MF(i, j, 0, 1);
-        DCX_MF(i, j, 0, 0);
-      }
-#undef DCX_MF
+    x6_products(acc, af, bfr);
     if constexpr (NL > 0) {
       constexpr int G = 24 / (NL + 1);
 #pragma unroll
@@ -453,9 +219,6 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_x6lm(const ConvParams p) {
     }
     __builtin_amdgcn_s_setprio(0);
   };
-  auto adv = [&](int& c_, int& m_) {
-    if (++m_ == taps) { m_ = 0; ++c_; }
-  };
   // loads of step (cl, ml) into register set Q: the input chunk when the step opens one (1-tap:
   // every step, clamped past the end, so unconditional), then the weight tile (clamped past the
   // end, unconditional).  With a halo the input-chunk loads go out before the MFMA cluster and
@@ -465,61 +228,59 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_x6lm(const ConvParams p) {
   auto load_pre = [&](auto qtag) {
     constexpr int Q = decltype(qtag)::value;
     if constexpr (HALO > 0)
-      if (ml == 0 && cl < nchunks) loadA(cl, ra[Q]);
+      if (ml == 0 && cl < nchunks) st.loadA(cl, ra[Q]);
   };
   auto load_in = [&](auto qtag) {
     constexpr int Q = decltype(qtag)::value;
     return [&]() {
-      if constexpr (HALO == 0) loadA(min(cl, nchunks - 1), ra[Q]);
-      loadB(min(cl, nchunks - 1), cl < nchunks ? ml : taps - 1, rb[Q]);
+      if constexpr (HALO == 0) st.loadA(min(cl, nchunks - 1), ra[Q]);
+      st.loadB(min(cl, nchunks - 1), cl < nchunks ? ml : taps - 1, rb[Q]);
     };
   };
   auto load_step = [&](auto qtag) {  // prologue: plain
     constexpr int Q = decltype(qtag)::value;
-    if (ml == 0 && cl < nchunks) loadA(cl, ra[Q]);
-    loadB(min(cl, nchunks - 1), cl < nchunks ? ml : taps - 1, rb[Q]);
-    adv(cl, ml);
+    if (ml == 0 && cl < nchunks) st.loadA(cl, ra[Q]);
+    st.loadB(min(cl, nchunks - 1), cl < nchunks ? ml : taps - 1, rb[Q]);
+    step_adv(cl, ml, taps);
   };
 
   // ---- prologue: steps 0 and 1 to LDS, step 2 into register set 0
-  loadA(0, ra[0]);
-  loadB(0, 0, rb[0]);
-  storeA(0, ra[0]);
-  storeB(0, rb[0]);
+  st.loadA(0, ra[0]);
+  st.loadB(0, 0, rb[0]);
+  st.storeA(0, ra[0]);
+  st.storeB(0, rb[0]);
   int c1 = 0, m1 = 0;  // position of step 1
-  adv(c1, m1);
-  loadB(c1, m1, rb[1]);
-  if (m1 == 0) loadA(1, ra[1]);  // taps == 1
-  storeB(1, rb[1]);
-  if (m1 == 0) storeA(1, ra[1]);
+  step_adv(c1, m1, taps);
+  st.loadB(c1, m1, rb[1]);
+  if (m1 == 0) st.loadA(1, ra[1]);  // taps == 1
+  st.storeB(1, rb[1]);
+  if (m1 == 0) st.storeA(1, ra[1]);
   cl = c1;
   ml = m1;
-  adv(cl, ml);                   // step 2
+  step_adv(cl, ml, taps);        // step 2
   int cw = cl, mw = ml;          // next step this group stores: 2
   load_step(std::integral_constant<int, 0>{});  // step 2 -> set 0; next load: step 3
   __syncthreads();
-#ifdef DCX_CLOCK_DIAG
-  const unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
-#endif
+  DCX_CLOCK_BEGIN;
   int cr = 0, mr = 0;
   if (group == 0) {
-    readF(0, 0, 0);
-    adv(cr, mr);
+    st.readF(0, 0, 0, af, bfr);
+    step_adv(cr, mr, taps);
     // iteration s: MFMA(s) (after loading step s+3 into set (s+1) & 1), then MEM0(s): fragments
     // of step s+1, store step s+2 from set s & 1
     auto iter = [&](int s, auto qtag) {
       constexpr int Q = decltype(qtag)::value;  // s & 1
       load_pre(std::integral_constant<int, 1 - Q>{});
       mfma_with(std::integral_constant<int, NL>{}, load_in(std::integral_constant<int, 1 - Q>{}));
-      adv(cl, ml);
+      step_adv(cl, ml, taps);
       __syncthreads();
-      if (s + 1 < nsteps) readF(cr, mr, (s + 1) & 1);
+      if (s + 1 < nsteps) st.readF(cr, mr, (s + 1) & 1, af, bfr);
       if (s + 2 < nsteps) {
-        storeB((s + 2) & 1, rb[Q]);
-        if (mw == 0) storeA(cw & 1, ra[Q]);
+        st.storeB((s + 2) & 1, rb[Q]);
+        if (mw == 0) st.storeA(cw & 1, ra[Q]);
       }
-      adv(cr, mr);
-      adv(cw, mw);
+      step_adv(cr, mr, taps);
+      step_adv(cw, mw, taps);
       __syncthreads();
     };
     for (int s = 0; s < nsteps; s += 2) {
@@ -531,17 +292,17 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_x6lm(const ConvParams p) {
     // from the prologue); then MFMA(s) after loading step s+3 into set (s+1) & 1
     auto iter = [&](int s, auto qtag) {
       constexpr int Q = decltype(qtag)::value;  // s & 1
-      readF(cr, mr, s & 1);
+      st.readF(cr, mr, s & 1, af, bfr);
       if (s >= 1 && s + 1 < nsteps) {
-        storeB((s + 1) & 1, rb[1 - Q]);
-        if (mw == 0) storeA(cw & 1, ra[1 - Q]);
+        st.storeB((s + 1) & 1, rb[1 - Q]);
+        if (mw == 0) st.storeA(cw & 1, ra[1 - Q]);
       }
-      if (s >= 1) adv(cw, mw);
-      adv(cr, mr);
+      if (s >= 1) step_adv(cw, mw, taps);
+      step_adv(cr, mr, taps);
       __syncthreads();
       load_pre(std::integral_constant<int, 1 - Q>{});
       mfma_with(std::integral_constant<int, NL>{}, load_in(std::integral_constant<int, 1 - Q>{}));
-      adv(cl, ml);
+      step_adv(cl, ml, taps);
       __syncthreads();
     };
     for (int s = 0; s < nsteps; s += 2) {
@@ -549,14 +310,8 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_x6lm(const ConvParams p) {
       iter(s + 1, std::integral_constant<int, 1>{});
     }
   }
-#ifdef DCX_CLOCK_DIAG
-  if (threadIdx.x == 0) {
-    atomicAdd(&g_clock_diag[0], __builtin_amdgcn_s_memtime() - t0);
-    atomicAdd(&g_clock_diag[1], __builtin_amdgcn_s_memrealtime() - r0);
-    atomicAdd(&g_clock_diag[2], (unsigned long long)nsteps);
-  }
-#endif
-  epilogue_lds<BM, BN, 4, WN, (2 * ABUF + 2 * BBUF) / 2, 512, HALO ? 0 : 2>(p, p, acc, q0, co0, b, ph, reinterpret_cast<float*>(lds));
+  DCX_CLOCK_END(nsteps);
+  epilogue_lds<BM, BN, 4, WN, S::LDS_US / 2, 512, HALO ? 0 : 2>(p, p, acc, g.q0, g.co0, b, ph, reinterpret_cast<float*>(lds));
 }
 
 template <int HALO, int BN, bool AF32 = false>
@@ -569,19 +324,12 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_x6pp(const ConvParams p) {
 
 // Grouped split-K launch (round 4, the split-K latency mode): up to 3 independent halo convs (the
 // three ResBlocks' convs of one dilation index) in one grid, member k with its own K-slice count
-// (ConvParams::ksplit; its clips are virtual: slice * clips + clip).  Member by raw block index, the
-// XCD remap inside the member, as conv_gemm_x6dq_group.
+// (ConvParams::ksplit; its clips are virtual: slice * clips + clip).  Members as group_member deals them.
 __global__ void __launch_bounds__(512, 2) conv_gemm_x6pp_group(const ConvGroup g) {
-  const int t = blockIdx.x;
-  const int k = t >= g.start[1] ? (t >= g.start[2] ? 2 : 1) : 0;
-  const int local = xcd_remap(t - g.start[k], g.start[k + 1] - g.start[k]);
-  const int b = local / g.tiles_per_clip[k];
-  ConvParams p;  // a private copy of the main-loop fields (pr: the range fields, read in place by the epilogue)
-  if (k == 0) p = g.p[0];
-  else if (k == 1) p = g.p[1];
-  else p = g.p[2];
-  const ConvParams& pr = k == 0 ? g.p[0] : k == 1 ? g.p[1] : g.p[2];
-  x6pp_tile<64, 128>(p, pr, local - b * g.tiles_per_clip[k], b, 0);
+  ConvParams p;
+  int local, b;
+  const ConvParams& pr = group_member(g, p, local, b);
+  x6pp_tile<64, 128>(p, pr, local, b, 0);
 }
 
 template <int HALO>
@@ -639,27 +387,13 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_x6dm(const ConvParams p) {
   static_assert(LDS_US * 2 <= 160 * 1024, "LDS");
   __shared__ __attribute__((aligned(16))) unsigned short lds[LDS_US];
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int group = __builtin_amdgcn_readfirstlane(tid >> 8);
-  const int gw = __builtin_amdgcn_readfirstlane((tid >> 6) & 3);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int ntiles = p.Cout / BN;
   int wg, b, ph;
-  flat_tile(((p.Lq + BM - 1) / BM) * ntiles, p.batch, wg, b, ph);
-  const int mt = wg / ntiles, nt = wg - mt * ntiles;
-  const int q0 = mt * BM, co0 = nt * BN;
-  const int nchunks = p.Cin / BK;
-  const int taps = p.taps;
-  const int nsteps = nchunks * taps;
-  const int lo_rel = p.in_step < 0 ? (taps - 1) * p.in_step : 0;
-  const int row0 = q0 + p.in_base[ph] + lo_rel;
+  flat_tile(((p.Lq + BM - 1) / BM) * (p.Cout / BN), p.batch, wg, b, ph);
+  const TileGeo g = tile_geo<BM, BN, WN>(p, wg, ph, p.Cin / BK);
+  const int lane = g.lane, group = g.group, gw = g.gw, wm = g.wm, wn = g.wn, q0 = g.q0, co0 = g.co0;
+  const int nchunks = g.nchunks, taps = g.taps, nsteps = g.nsteps, lo_rel = g.lo_rel, row0 = g.row0;
   const int arow = p.ldx * 6;  // bytes per planes row
-  // halo: descriptor over the clip (negative rows wrap past its range: zeros); 1-tap: over the
-  // tile's rows only, so clips of any length keep 32-bit offsets (row0 >= 0 without a halo)
-  const __amdgpu_buffer_rsrc_t rx =
-      HALO ? __builtin_amdgcn_make_buffer_rsrc((void*)(p.x6 + (long long)b * p.x_bstride * 3), 0, p.Lin * arow, 0x00020000)
-           : __builtin_amdgcn_make_buffer_rsrc((void*)(p.x6 + ((long long)b * p.x_bstride + (long long)row0 * p.ldx) * 3), 0,
-                                               max(0, min(BM, p.Lin - row0)) * arow, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rx = x_desc<6, HALO>(p, b, row0, BM);
   const int rbase = HALO ? row0 : 0;  // row of image row 0 relative to the descriptor
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(p.w6 + (long long)ph * taps * nchunks * p.Cout * 48), 0, taps * nchunks * p.Cout * 96, 0x00020000);
@@ -726,52 +460,25 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_x6dm(const ConvParams p) {
     }
   };
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-  auto mfma = [&]() {
-    __builtin_amdgcn_s_setprio(1);
-#define DCX_MF(i, j, x, y) \
-  acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af[i][x]), \
-                                                      __builtin_bit_cast(bf16x8, bfr[j][y]), acc[i][j], 0, 0, 0)
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        DCX_MF(i, j, 2, 0);
-        DCX_MF(i, j, 1, 1);
-        DCX_MF(i, j, 0, 2);
-        DCX_MF(i, j, 1, 0);
-        DCX_MF(i, j, 0, 1);
-        DCX_MF(i, j, 0, 0);
-      }
-#undef DCX_MF
-    __builtin_amdgcn_s_setprio(0);
-  };
-  auto adv = [&](int& c_, int& m_) {
-    if (++m_ == taps) { m_ = 0; ++c_; }
-  };
-  auto inc3 = [](int& slot) { slot = slot == 2 ? 0 : slot + 1; };
+  DCX_ZERO_ACC16(acc, TM, TN);
+  auto mfma = [&]() { x6_mfma_segment(acc, af, bfr); };
 
+  // The schedule of pingpong3_loop (fragments first), written out: on the shared driver hipcc walked
+  // the ring with other scalar code and this kernel measured 0.4-1.9 % slower at 1024 -> 4096
+  // (profiles/conv_fold_ab.md).
   // ---- prologue: steps 0, 1, 2 (both groups their pieces), drained
   int cl = 0, ml = 0;
   for (int t = 0; t < 3; ++t) {
     if (t < nsteps) dma_step(cl, ml, t);
-    adv(cl, ml);
+    step_adv(cl, ml, taps);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  seg_barrier();
-#ifdef DCX_CLOCK_DIAG
-  const unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
-#endif
+  pingpong3_drain();
+  DCX_CLOCK_BEGIN;
   // cl, ml: step 3, the next step either group issues
   int cr = 0, mr = 0;
   if (group == 0) {
     readF(0, 0, 0);
-    adv(cr, mr);
+    step_adv(cr, mr, taps);
     int rs = 1, ws = 0;  // slot of the step read next (s + 1), of the step issued next (s + 3)
     for (int s = 0; s < nsteps; ++s) {
       mfma();  // MFMA(s)
@@ -782,10 +489,10 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_x6dm(const ConvParams p) {
       if (s + 3 < nsteps) n = dma_step(cl, ml, ws);
       wait_dma(n);
       seg_barrier();
-      adv(cr, mr);
-      adv(cl, ml);
-      inc3(rs);
-      inc3(ws);
+      step_adv(cr, mr, taps);
+      step_adv(cl, ml, taps);
+      ring_inc(rs);
+      ring_inc(ws);
     }
   } else {
     int rs = 0, ws = 0;  // slot of step s, of step s + 2
@@ -795,26 +502,19 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_x6dm(const ConvParams p) {
       int n = 0;
       if (s >= 1 && s + 2 < nsteps) {
         n = dma_step(cl, ml, ws);
-        adv(cl, ml);
+        step_adv(cl, ml, taps);
       }
       wait_dma(n);
       seg_barrier();
       mfma();  // MFMA(s)
       seg_barrier();
-      adv(cr, mr);
-      inc3(rs);
-      if (s >= 1) inc3(ws);
-      else ws = 0;  // step 3's slot
+      step_adv(cr, mr, taps);
+      ring_inc(rs);
+      ring_inc_issue1(ws, s);
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef DCX_CLOCK_DIAG
-  if (threadIdx.x == 0) {  // steps counted in units of x6pp's (half the MFMAs)
-    atomicAdd(&g_clock_diag[0], __builtin_amdgcn_s_memtime() - t0);
-    atomicAdd(&g_clock_diag[1], __builtin_amdgcn_s_memrealtime() - r0);
-    atomicAdd(&g_clock_diag[2], 2ull * nsteps);
-  }
-#endif
+  DCX_CLOCK_END(2ull * nsteps);  // steps counted in units of x6pp's (half the MFMAs)
   epilogue_lds<BM, BN, 4, WN, LDS_US / 2, 512, HALO ? 0 : 2>(p, p, acc, q0, co0, b, ph, reinterpret_cast<float*>(lds));
 }
 
@@ -854,21 +554,11 @@ __device__ __forceinline__ void x6dq_tile(const ConvParams& p, const ConvParams&
   static_assert(LDS_US * 2 <= 160 * 1024, "LDS");
   __shared__ __attribute__((aligned(16))) unsigned short lds[LDS_US];
 
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int group = __builtin_amdgcn_readfirstlane(tid >> 8);
-  const int gw = __builtin_amdgcn_readfirstlane((tid >> 6) & 3);
-  const int wm = wave >> 1, wn = wave & 1;
-  const int ntiles = p.Cout / BN;
-  const int mt = wg / ntiles, nt = wg - mt * ntiles;
-  const int q0 = mt * BM, co0 = nt * BN;
-  const int nchunks = p.Cin / BK;
-  const int taps = p.taps;
-  const int nsteps = nchunks * taps;
-  const int lo_rel = p.in_step < 0 ? (taps - 1) * p.in_step : 0;
-  const int row0 = q0 + p.in_base[ph] + lo_rel;
+  const TileGeo g = tile_geo<BM, BN, WN>(p, wg, ph, p.Cin / BK);
+  const int lane = g.lane, group = g.group, gw = g.gw, wm = g.wm, wn = g.wn, co0 = g.co0;
+  const int nchunks = g.nchunks, taps = g.taps, nsteps = g.nsteps, lo_rel = g.lo_rel, row0 = g.row0;
   const int arow = p.ldx * 6;
-  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(p.x6 + (long long)b * p.x_bstride * 3), 0, p.Lin * arow, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rx = x_desc_clip<6>(p, b);
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(p.w6 + (long long)ph * taps * nchunks * p.Cout * 48), 0, taps * nchunks * p.Cout * 96, 0x00020000);
 
@@ -934,10 +624,7 @@ __device__ __forceinline__ void x6dq_tile(const ConvParams& p, const ConvParams&
     for (int k = 0; k < RH; ++k) readA(k, k);
   };
   f32x4 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   // MFMA segment: row block by row block, and within a block operand set by operand set (per
   // accumulator: lh' + hl', then mh' + hm', then hh' + mm'); as soon as a set's MFMAs are issued,
   // its registers take the same set of row block rb + RH (read from the same step's image), so the
@@ -966,29 +653,24 @@ __device__ __forceinline__ void x6dq_tile(const ConvParams& p, const ConvParams&
       }
     __builtin_amdgcn_s_setprio(0);
   };
-  auto adv = [&](int& c_, int& m_) {
-    if (++m_ == taps) { m_ = 0; ++c_; }
-  };
-  auto inc3 = [](int& slot) { slot = slot == 2 ? 0 : slot + 1; };
 
+  // conv_gemm_x6dm's loop (written out for the same reason: res128_k11 measured 0.7-1.0 % slower on
+  // the shared driver), with the first four DCX_SEG_DIAG slots of pingpong3_loop
   int cl = 0, ml = 0;
   for (int tt = 0; tt < 3; ++tt) {
     if (tt < nsteps) dma_step(cl, ml, tt);
-    adv(cl, ml);
+    step_adv(cl, ml, taps);
   }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  seg_barrier();
+  pingpong3_drain();
   DCX_TILET(tile_t1);
-#ifdef DCX_CLOCK_DIAG
-  const unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
-#endif
+  DCX_CLOCK_BEGIN;
   int cr = 0, mr = 0;
 #ifdef DCX_SEG_DIAG
   unsigned long long sd[4] = {};
 #endif
   if (group == 0) {
     readF(0, 0, 0);
-    adv(cr, mr);
+    step_adv(cr, mr, taps);
     int rs = 1, ws = 0;
     for (int s = 0; s < nsteps; ++s) {
       DCX_SEGT(ta);
@@ -1006,10 +688,10 @@ __device__ __forceinline__ void x6dq_tile(const ConvParams& p, const ConvParams&
 #ifdef DCX_SEG_DIAG
       sd[0] += tb - ta; sd[1] += tc - tb; sd[2] += td - tc; sd[3] += te - td;
 #endif
-      adv(cr, mr);
-      adv(cl, ml);
-      inc3(rs);
-      inc3(ws);
+      step_adv(cr, mr, taps);
+      step_adv(cl, ml, taps);
+      ring_inc(rs);
+      ring_inc(ws);
     }
   } else {
     int rs = 0, ws = 0;
@@ -1019,7 +701,7 @@ __device__ __forceinline__ void x6dq_tile(const ConvParams& p, const ConvParams&
       int n = 0;
       if (s >= 1 && s + 2 < nsteps) {
         n = dma_step(cl, ml, ws);
-        adv(cl, ml);
+        step_adv(cl, ml, taps);
       }
       wait_dma(n);
       DCX_SEGT(tb);
@@ -1032,10 +714,9 @@ __device__ __forceinline__ void x6dq_tile(const ConvParams& p, const ConvParams&
 #ifdef DCX_SEG_DIAG
       sd[2] += tb - ta; sd[3] += tc - tb; sd[0] += td - tc; sd[1] += te - td;
 #endif
-      adv(cr, mr);
-      inc3(rs);
-      if (s >= 1) inc3(ws);
-      else ws = 0;
+      step_adv(cr, mr, taps);
+      ring_inc(rs);
+      ring_inc_issue1(ws, s);
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -1046,29 +727,10 @@ __device__ __forceinline__ void x6dq_tile(const ConvParams& p, const ConvParams&
     if (group == 0) atomicAdd(&g_seg_diag[12], (unsigned long long)nsteps);
   }
 #endif
-#ifdef DCX_CLOCK_DIAG
-  if (threadIdx.x == 0) {
-    atomicAdd(&g_clock_diag[0], __builtin_amdgcn_s_memtime() - t0);
-    atomicAdd(&g_clock_diag[1], __builtin_amdgcn_s_memrealtime() - r0);
-    atomicAdd(&g_clock_diag[2], 2ull * nsteps);
-  }
-#endif
+  DCX_CLOCK_END(2ull * nsteps);
   DCX_TILET(tile_t2);
-  epilogue_lds<BM, BN, 4, WN, LDS_US / 2, 512, 0>(p, pr, acc, q0, co0, b, ph, reinterpret_cast<float*>(lds));
-#ifdef DCX_TILE_DIAG
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned long long t3 = __builtin_amdgcn_s_memrealtime();
-    const unsigned int k = atomicAdd(&g_tile_cnt, 1u);
-    if (k < (unsigned)kTileDiagMax) {
-      unsigned long long* o = g_tile_diag + 6ull * k;
-      o[0] = tile_t0; o[1] = tile_t1; o[2] = tile_t2; o[3] = t3;
-      o[4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
-      o[5] = __builtin_amdgcn_s_getreg((15 << 11) | 20);
-    }
-  }
-#endif
+  epilogue_lds<BM, BN, 4, WN, LDS_US / 2, 512, 0>(p, pr, acc, g.q0, co0, b, ph, reinterpret_cast<float*>(lds));
+  DCX_TILE_END(0);
 }
 
 template <int BN>
@@ -1082,21 +744,10 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_x6dq(const ConvParams p) {
 // dilation index, tap counts 3 / 7 / 11), longest first, so the short ones fill the last round.
 template <int BN>
 __global__ void __launch_bounds__(512, 2) conv_gemm_x6dq_group(const ConvGroup g) {
-  // member by raw block index, so every XCD (block index mod 8) gets its share of each member's
-  // tiles; a remap of the whole grid would hand the 11-tap tiles to the first XCDs and the 3-tap
-  // ones to the last
-  const int t = blockIdx.x;
-  const int k = t >= g.start[1] ? (t >= g.start[2] ? 2 : 1) : 0;
-  const int local = xcd_remap(t - g.start[k], g.start[k + 1] - g.start[k]);
-  const int b = local / g.tiles_per_clip[k];
-  // a private copy: the tile body's inline-asm barriers clobber memory, which would make the
-  // compiler re-read every field of a kernarg-resident struct after each of them
-  ConvParams p;  // a private copy of the main-loop fields (pr: the range fields, read in place by the epilogue)
-  if (k == 0) p = g.p[0];
-  else if (k == 1) p = g.p[1];
-  else p = g.p[2];
-  const ConvParams& pr = k == 0 ? g.p[0] : k == 1 ? g.p[1] : g.p[2];
-  x6dq_tile<BN>(p, pr, local - b * g.tiles_per_clip[k], b, 0);
+  ConvParams p;
+  int local, b;
+  const ConvParams& pr = group_member(g, p, local, b);
+  x6dq_tile<BN>(p, pr, local, b, 0);
 }
 
 template <int BN>

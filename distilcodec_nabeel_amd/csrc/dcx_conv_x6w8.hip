@@ -5,6 +5,7 @@
 
 #include "dcx_conv_common.h"
 #include "dcx_conv_launch.h"
+#include "dcx_conv_pingpong.h"
 
 namespace dcx {
 
@@ -194,16 +195,8 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_gemm_x6w8(const ConvPara
   };
 
   f32x16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+  DCX_ZERO_ACC16(acc, TM, TN);
 
-  auto adv = [&](int& c_, int& m_) {
-    if (++m_ == taps) { m_ = 0; ++c_; }
-  };
   // step positions (chunk, tap) of s+1, s+2, s+3 and the ring slot of step s
   int c1, m1, c2, m2, c3, m3, slot;
   // ---- prologue, part 1 (issued before the previous tile's epilogue): A(0), B(0), B(1), and
@@ -227,10 +220,10 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_gemm_x6w8(const ConvPara
     m1 = s1m;
     c2 = c1;
     m2 = m1;
-    adv(c2, m2);
+    step_adv(c2, m2, taps);
     c3 = c2;
     m3 = m2;
-    adv(c3, m3);
+    step_adv(c3, m3, taps);
     slot = 0;
     if constexpr (HALO > 0) {
       if (nchunks > 1) loadA(1, ra[0]);
@@ -260,50 +253,26 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_gemm_x6w8(const ConvPara
     }
     loadB(min(c3, nchunks - 1), c3 < nchunks ? m3 : taps - 1, rb[Q]);
     // 3. MFMAs of step s
-#define DCX_MF(i, j, x, y) \
-  acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af[Q][i][x]), \
-                                                      __builtin_bit_cast(bf16x8, bfr[Q][j][y]), acc[i][j], 0, 0, 0)
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        if constexpr (PROD == 6) {
-          DCX_MF(i, j, 2, 0);
-          DCX_MF(i, j, 1, 1);
-          DCX_MF(i, j, 0, 2);
-          DCX_MF(i, j, 1, 0);
-          DCX_MF(i, j, 0, 1);
-        }
-        DCX_MF(i, j, 0, 0);
-      }
-#undef DCX_MF
+    x6_products<PROD>(acc, af[Q], bfr[Q]);
     // 4. stage step s+2: weight tile into its ring slot; its input chunk if s+2 opens one
     storeB(slot2, rb[1 - Q]);
     if (m2 == 0 && c2 < nchunks) storeA(c2 & 1, ra[(1 - Q) % RA_SETS]);
     __syncthreads();
-    adv(c1, m1);
-    adv(c2, m2);
-    adv(c3, m3);
+    step_adv(c1, m1, taps);
+    step_adv(c2, m2, taps);
+    step_adv(c3, m3, taps);
     slot = slot1;
   };
   for (;;) {
     prologue_stores();
     // nsteps is even (launcher): without an odd exit the loop header never merges a path on which
     // this iteration's loads are still in flight, which made the waitcnt pass emit vmcnt(0).
-#ifdef DCX_CLOCK_DIAG
-    const unsigned long long t0 = __builtin_amdgcn_s_memtime(), r0 = __builtin_amdgcn_s_memrealtime();
-#endif
+    DCX_CLOCK_BEGIN;
     for (int s = 0; s < nsteps; s += 2) {
       step(s, std::integral_constant<int, 0>{});
       step(s + 1, std::integral_constant<int, 1>{});
     }
-#ifdef DCX_CLOCK_DIAG
-    if (threadIdx.x == 0) {
-      atomicAdd(&g_clock_diag[0], __builtin_amdgcn_s_memtime() - t0);
-      atomicAdd(&g_clock_diag[1], __builtin_amdgcn_s_memrealtime() - r0);
-      atomicAdd(&g_clock_diag[2], (unsigned long long)nsteps);
-    }
-#endif
+    DCX_CLOCK_END(nsteps);
     // the next tile's first loads go out before this tile's epilogue, which hides their latency
     const int eq0 = q0, eco0 = co0, eb = b, eph = ph;
     const int Ln = L + G;
@@ -316,12 +285,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 2) conv_gemm_x6w8(const ConvPara
                                                                 reinterpret_cast<float*>(lds));
     if (!more) break;
     L = Ln;
-#pragma unroll
-    for (int i = 0; i < TM; ++i)
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    DCX_ZERO_ACC16(acc, TM, TN);
     __syncthreads();  // the epilogue's LDS reads are done before the next prologue writes LDS
   }
 }

@@ -279,3 +279,38 @@ def test_wide_stage_edge_lengths(eng, state, cfg, stage, L):
         assert torch.equal(y2, y), knobs
     for c in range(2):
         assert torch.equal(eng.module(name, xd[c:c + 1].contiguous())[0], y[c]), f"clip {c} alone differs from the batch"
+
+
+# The same stages under DCX_H3=0 at the lengths where the x6 path groups its 64K-output tiles
+# (conv_gemm_x6dq_group): a clip needs ceil(L / BM) * (C / BN) >= 16 tiles.  Stage 0 (C = 512, 256 x 256
+# tiles): 1793 is the first such length, and its eighth row tile holds one row; 2049 adds a ninth tile of
+# one row.  Stage 2 (C = 128, 512 x 128 tiles): 7681, whose sixteenth tile holds one row.
+X6DQ_GROUP = {0: "conv_gemm_x6dq_group<256,256,halo>", 2: "conv_gemm_x6dq_group<512,128,halo>"}
+
+
+@pytest.mark.parametrize("stage,L", [(0, 1793), (0, 2049), (2, 7681)])
+def test_x6_grouped_stage_lengths(eng, state, cfg, stage, L):
+    """generator.resblocks.{0,2} under DCX_H3=0 on two different clips: the grouped x6dq kernel and its
+    single launch by name, the x6 bound against the fp64 oracle per clip (1e-5 of the clip's maximum, as
+    tests/test_gpu_conv.py), and each clip alone the bits it has in the batch.  The stage 0 oracle of
+    both clips (2.7e11 fp64 FLOPs) measured 5.7 s on 8 CPU threads, which is about 3 s on 16 at best, more than
+    a test case may spend on its reference; there it runs for the second clip only."""
+    from oracle import reference_cpu as R
+
+    name = f"generator.resblocks.{stage}"
+    C = cfg["decoder"]["upsample_initial_channel"] >> (stage + 1)
+    x = torch.from_numpy(np.random.default_rng(2000 * stage + L).standard_normal((2, C, L)).astype(np.float32))
+    clips = (1,) if stage == 0 else (0, 1)
+    ref = {c: torch.nn.functional.silu(R.parallel_block(x[c:c + 1].double(), state["generator"], stage, cfg["decoder"],
+                                                        torch.float64))[0].numpy() for c in clips}
+    xd = _cl(x.numpy())
+    with eng.knobs(DCX_H3=0):
+        y, names = _module_kernels(eng, name, xd)
+        alone = [eng.module(name, xd[c:c + 1].contiguous())[0] for c in range(2)]
+    assert names == _group_and_single(X6DQ_GROUP[stage]), names
+    yn = y.cpu().numpy().transpose(0, 2, 1)
+    errs = {c: _rel(yn[c], ref[c]) for c in clips}
+    print(f"\nstage {stage} (C = {C}) L = {L}: x6 rel err per clip {errs}", end="")
+    assert max(errs.values()) <= 1e-5, errs
+    for c in range(2):
+        assert torch.equal(alone[c], y[c]), f"clip {c} alone differs from the batch"
