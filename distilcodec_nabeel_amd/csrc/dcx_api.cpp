@@ -577,7 +577,7 @@ int dcx_conv_forward(dcx_conv* c, int32_t gemm_mode, const float* x, int32_t bat
         xa.r.amax = am;
       } else {
         if (dcx::launch_h2_rows(x, c->planes, rows, c->w.cin, ash, s) != hipSuccess)
-          return fail(h, DCX_ERR_HIP, "h3 input split (per row) failed: Cin must be 256, 512, 768 or 1024");
+          return fail(h, DCX_ERR_HIP, "h3 input split (per row) failed: Cin must be 256, 512, 768, 1024 or a multiple of 32 below 256");
         xa.r.ash_row = ash;
       }
       xa.h2 = true;

@@ -3,6 +3,7 @@
 #include "dcx_conv_common.h"
 #include "dcx_conv_launch.h"
 #include "dcx_conv_pingpong.h"
+#include "dcx_w3_layout.h"
 
 namespace dcx {
 
@@ -70,10 +71,11 @@ __device__ __forceinline__ void x3dq_tile(const ConvParams& p, const ConvParams&
   const __amdgpu_buffer_rsrc_t rx = x_desc<4, HALO>(p, b, row0, BM);
   const int rbase = HALO ? row0 : 0;  // row of image row 0 relative to the descriptor
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(p.w3 + (long long)ph * taps * nchunks * p.Cout * 64), 0, taps * nchunks * p.Cout * 128, 0x00020000);
+      (void*)(p.w3 + w3_step(taps, p.Cin, p.Cout, ph, 0, 0)), 0, taps * nchunks * p.Cout * 128, 0x00020000);
 
   // DMA: group instruction k fills 64 rows of piece (k * 64) / rows; the wave's i-th is k = i * 4 + gw.
-  // Source of piece pc in an h2 row's chunk: channel group pc & 3 at 32 B, plane pc >> 2 at 16 B.
+  // Source of piece pc in an h2 row's chunk: channel group pc & 3 at 32 B, plane pc >> 2 at 16 B;
+  // of the weights: dcx_w3_layout.h (the wide flavour, each 64-column block in image order).
   int a_off[A_PW], b_off[B_PW];
 #pragma unroll
   for (int i = 0; i < A_PW; ++i) {
@@ -83,9 +85,7 @@ __device__ __forceinline__ void x3dq_tile(const ConvParams& p, const ConvParams&
   }
 #pragma unroll
   for (int i = 0; i < B_PW; ++i) {
-    const int u = (group * B_G + i * 4 + gw) * 64;
-    const int pc = u / BN, col = u - pc * BN + lane;
-    b_off[i] = (co0 + col) * 128 + (pc & 3) * 32 + (pc >> 2) * 16;
+    b_off[i] = w3_wide_lane(co0, lane) + w3_wide_piece(BN, group * B_G + i * 4 + gw);  // 1 KiB contiguous
   }
   unsigned short* const a_dst = lds + (group * A_G + gw) * 512;
   unsigned short* const b_dst = lds + NA * ABUF / 2 + (group * B_G + gw) * 512;
@@ -101,7 +101,7 @@ __device__ __forceinline__ void x3dq_tile(const ConvParams& p, const ConvParams&
         dma16(rx, a_dst + (HALO ? (c & 1) : slot) * (ABUF / 2) + i * 2048, a_off[i] + c * 128, 0);
       n += A_PW;
     }
-    const int soff = (m * nchunks + c) * p.Cout * 128;
+    const int soff = w3_step_bytes(nchunks, p.Cout, m, c);
 #pragma unroll
     for (int i = 0; i < B_PW; ++i) dma16(rw, b_dst + slot * (BBUF / 2) + i * 2048, b_off[i], soff);
     return n;
@@ -249,7 +249,7 @@ __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams&
   const __amdgpu_buffer_rsrc_t rx = x_desc<4, HALO>(p, b, row0, BM);
   const int rbase = HALO ? row0 : 0;  // row of image row 0 relative to the descriptor
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
-      (void*)(p.w3 + (long long)ph * taps * nchunks * p.Cout * 64), 0, taps * nchunks * p.Cout * 128, 0x00020000);
+      (void*)(p.w3 + w3_step(taps, p.Cin, p.Cout, ph, 0, 0)), 0, taps * nchunks * p.Cout * 128, 0x00020000);
 
   // DMA (group 0 alone): instruction k fills 64 rows of piece (k * 64) / rows; the wave's i-th is
   // k = i * 4 + gw.  Lane part of the source offset in one VGPR, the rest wave-uniform.  (Group 1
@@ -257,7 +257,7 @@ __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams&
   // flight in both segments, measured slower: C2 194.2-194.7 against 185.3-185.4 ms, r05n; the
   // issue stalls behind group 0's and holds up the MFMAs.)
   const int a_lane = (rbase + lane) * arow;  // negative rows: huge unsigned, out of range (zeros)
-  const int b_lane = (co0 + lane) * 128;
+  const int b_lane = w3_wide_lane(co0, lane);  // dcx_w3_layout.h: every weight piece is 1 KiB contiguous
   [[maybe_unused]] bool in_loop = false;  // -DDCX_X3_NODMA (diagnostic): no DMA after the prologue (wrong results)
   auto dmaA1 = [&](int c, int slot, int i) {  // the wave's i-th A piece of chunk c
 #ifdef DCX_X3_NODMA
@@ -279,9 +279,7 @@ __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams&
     if (in_loop) return;
 #endif
     const int k = (group ? B_G0 : 0) + i * 4 + gw;
-    const int u = k * 64, pc = u / BN, col = u - pc * BN;
-    dma16(rw, lds + NA * ABUF / 2 + slot * (BBUF / 2) + k * 512, b_lane + col * 128 + (pc & 3) * 32 + (pc >> 2) * 16,
-          (m * nchunks + c) * p.Cout * 128);
+    dma16(rw, lds + NA * ABUF / 2 + slot * (BBUF / 2) + k * 512, b_lane, w3_step_bytes(nchunks, p.Cout, m, c) + w3_wide_piece(BN, k));
   };
   auto dma_step = [&](int c, int m, int slot) {  // group 0's pieces of a step (its input chunk first)
     if (m == 0) {

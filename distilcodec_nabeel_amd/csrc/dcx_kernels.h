@@ -199,7 +199,8 @@ struct ConvParams {
   // a clip's bits must not depend on how many rows share its launch)
   int fixed_tiles;
   // h3 arithmetic (conv_gemm_x3dq, x_compact == 3: the input in the fp16 "h2" layout of
-  // dcx_planes.h): weights [phase][tap][Cin/32][Cout][4 groups][h 8 | l 8] fp16 of w * 2^w3_shift
+  // dcx_planes.h): weights fp16 h / l of w * 2^w3_shift, steps [phase][tap][Cin/32] of Cout * 128
+  // bytes, each in the order of dcx_w3_layout.h (w3_offset)
   const unsigned short* w3;
   int w3_shift;
   // y6s in the h2 layout instead of planes (the input of a following h3 conv)

@@ -408,10 +408,31 @@ __global__ void __launch_bounds__(256) h2_rows_kernel(const float* __restrict__ 
   for (int i = 0; i < NV; ++i) store_h2_4(y6, row, C, (lane + 64 * i) * 4, v[i].x, v[i].y, v[i].z, v[i].w, sc);
 }
 
+// rows narrower than a wave's 256 channels (C % 32 == 0, C < 256): the wave's first C / 4 lanes
+__global__ void __launch_bounds__(256) h2_rows_narrow_kernel(const float* __restrict__ x, unsigned short* __restrict__ y6,
+                                                              long long rows, int C, int* __restrict__ ash_row) {
+  const int lane = threadIdx.x & 63;
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const bool on = lane * 4 < C;
+  f32x4 v = {0.f, 0.f, 0.f, 0.f};
+  if (on) v = *reinterpret_cast<const f32x4*>(x + row * C + lane * 4);
+  float am = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) am = fmaxf(am, __shfl_xor(am, off, 64));
+  const int sh = h2_shift(am);
+  if (lane == 0) ash_row[row] = sh;
+  if (on) store_h2_4(y6, row, C, lane * 4, v.x, v.y, v.z, v.w, __builtin_ldexpf(1.0f, sh));
+}
+
 hipError_t launch_h2_rows(const float* x, unsigned short* y6, long long rows, int C, int* ash_row, hipStream_t s) {
   if (!x || !y6 || !ash_row || rows < 0) return hipErrorInvalidValue;
   if (rows == 0) return hipSuccess;
   dim3 grid((unsigned)((rows + 3) / 4)), block(256);
+  if (C > 0 && C < 256 && C % 32 == 0) {
+    hipLaunchKernelGGL(h2_rows_narrow_kernel, grid, block, 0, s, x, y6, rows, C, ash_row);
+    return hipGetLastError();
+  }
   switch (C) {
     case 256: hipLaunchKernelGGL(h2_rows_kernel<1>, grid, block, 0, s, x, y6, rows, ash_row); break;
     case 512: hipLaunchKernelGGL(h2_rows_kernel<2>, grid, block, 0, s, x, y6, rows, ash_row); break;

@@ -364,7 +364,7 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair_g(const ResPairParams p)
 // group kg = lane >> 4 holding channel group kg of both operands: half the MFMAs of x6, two fragment
 // reads per block and chunk instead of six, and images of 4 B per element instead of 6 (byte
 // ((chunk * 8 + piece) * NS + row) * 16, piece = plane * 4 + channel group).  Weights: the
-// ConvParams::w3 tap slices ([chunk][Cout][4][h' 8 | l' 8], scaled by 2^w3_shift per conv); the
+// ConvParams::w3 tap slices (dcx_w3_layout.h, the pair flavour; scaled by 2^w3_shift per conv); the
 // accumulators are scaled back before the bias.  Schedule, tiles and hand-offs are conv_res_pair_g's.
 // RAG: the ragged-batch instantiation (ResPairParams::clip_len honoured), launched only when the call
 // has lengths: the kernels sit at the register limit, and with the length code in the one instantiation
@@ -416,9 +416,7 @@ __global__ void __launch_bounds__(512, 1) conv_res_pair_h3(const ResPairParams p
   int dsrc[PPW];                     // per-lane source offsets of this wave's pieces
 #pragma unroll
   for (int i = 0; i < PPW; ++i) {
-    const int pc = min(wave + 8 * i, NP - 1);
-    const int pl = pc & 1, cbk = (pc >> 1) % (C / 16), ch = (pc >> 1) / (C / 16);
-    dsrc[i] = (ch * C + cbk * 16 + ln.l15) * 128 + (lane >> 4) * 32 + pl * 16;
+    dsrc[i] = w3_pair_piece(C, min(wave + 8 * i, NP - 1), lane);  // the piece's 1 KiB, contiguous (dcx_w3_layout.h)
   }
   // members' weights and tap counts picked by uniform selects (an index into the kernel-argument
   // arrays became a vector load that hipcc then waited for with vmcnt(0), DMA in flight included)

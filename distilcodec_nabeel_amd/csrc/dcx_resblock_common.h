@@ -7,6 +7,7 @@
 #pragma once
 #include "dcx_kernels.h"
 #include "dcx_planes.h"
+#include "dcx_w3_layout.h"
 
 namespace dcx {
 
@@ -97,7 +98,8 @@ struct RpX6 {
 };
 
 // h3 (conv_res_pair_h3): fp16 h / l per element scaled by a power of two, piece = plane * 4 + channel
-// group of a 32-channel chunk; weights [chunk][Cout][4][h' 8 | l' 8], the ConvParams::w3 tap slice.
+// group of a 32-channel chunk; weights: the ConvParams::w3 tap slice in the pair flavour of
+// dcx_w3_layout.h, [chunk][16-column block][h' | l'][K group 4][16 columns][16 B].
 // The lane holds channel group kg = lane >> 4 of both operands.
 struct RpH3 {
   static constexpr int PPC = 8, CW = 32, WB = 4;
@@ -119,10 +121,11 @@ struct RpH3 {
     *reinterpret_cast<vec*>(d) = hv;
     *reinterpret_cast<vec*>(d + 4 * ps) = lv;
   }
-  struct Wo { int o0, o1; };  // h' and l' of the lane's channel group
+  // h' and l' of the lane's channel group in column block 2 * wc of chunk 0; a column block is 2 KiB
+  // and a chunk C * 128 B further, as in x6's slices of WROW bytes per column (rp_load_wf)
+  struct Wo { int o0, o1; };
   __device__ static __forceinline__ Wo wo(int lane, int wc) {
-    const int base = ((2 * wc) * 16 + (lane & 15)) * 128 + (lane >> 4) * 32;
-    return {base, base + 16};
+    return {w3_pair_lane(2 * wc * 16, lane, 0), w3_pair_lane(2 * wc * 16, lane, 1)};
   }
   // lane parts of the two activation reads (h and l pieces of the lane's channel group, row within
   // the 16-row block); a tap adds its wave-uniform row offset once, row block / chunk offsets are

@@ -1,6 +1,7 @@
 // Checkpoint ingestion of the host runtime: weight-norm folding (fp64), packing into the kernels'
 // layouts, the mel front end's bases, the decode tables, the h3 range bounds of every conv.
 #include "dcx_host.h"
+#include "dcx_w3_layout.h"
 
 namespace dcx::host {
 
@@ -112,8 +113,9 @@ struct Builder {
           }
     return upload16(out);
   }
-  // fp32 packed [phases][cout][taps][cin] -> h3 layout [phase][tap][cin/32][cout][4 groups][h 8 | l 8]
-  // fp16 of w * 2^shift, shift putting the largest |w| in [2^14, 2^15) (conv_gemm_x3dq / x3dw)
+  // fp32 packed [phases][cout][taps][cin] -> the h3 weights, fp16 h / l of w * 2^shift at w3_offset
+  // (dcx_w3_layout.h: steps in [phase][tap][cin/32] order, a step's cout * 64 halves in the flavour
+  // cout selects), shift putting the largest |w| in [2^14, 2^15) (conv_gemm_x3dq / x3dw, the pair kernels)
   unsigned short* h2_pack(const std::vector<float>& pk, int phases, int cout, int taps, int cin, int& shift) {
     if (bad() || dry) return nullptr;
     float mx = 0.f;
@@ -121,22 +123,19 @@ struct Builder {
     int e = 0;
     if (mx > 0.f) std::frexp(mx, &e);  // mx = f * 2^e, f in [0.5, 1)
     shift = mx > 0.f ? 15 - e : 0;
-    const int nch = cin / 32;
-    std::vector<unsigned short> out((size_t)phases * taps * nch * cout * 64);
+    std::vector<unsigned short> out((size_t)phases * taps * cin * cout * 2);
     for (int r = 0; r < phases; ++r)
     for (int m = 0; m < taps; ++m)
-      for (int c = 0; c < nch; ++c)
-        for (int o = 0; o < cout; ++o) {
-          unsigned short* dst = &out[((((size_t)r * taps + m) * nch + c) * cout + o) * 64];
-          const float* src = &pk[(((size_t)r * cout + o) * taps + m) * cin + c * 32];
-          for (int j = 0; j < 32; ++j) {
-            const float x = std::ldexp(src[j], shift);
-            const _Float16 hh = (_Float16)x;
-            const _Float16 ll = (_Float16)(x - (float)hh);
-            dst[(j >> 3) * 16 + (j & 7)] = __builtin_bit_cast(unsigned short, hh);
-            dst[(j >> 3) * 16 + 8 + (j & 7)] = __builtin_bit_cast(unsigned short, ll);
-          }
+      for (int o = 0; o < cout; ++o) {
+        const float* src = &pk[(((size_t)r * cout + o) * taps + m) * cin];
+        for (int j = 0; j < cin; ++j) {
+          const float x = std::ldexp(src[j], shift);
+          const _Float16 hh = (_Float16)x;
+          const _Float16 ll = (_Float16)(x - (float)hh);
+          out[(size_t)w3_offset(taps, cin, cout, r, m, j, o, 0)] = __builtin_bit_cast(unsigned short, hh);
+          out[(size_t)w3_offset(taps, cin, cout, r, m, j, o, 1)] = __builtin_bit_cast(unsigned short, ll);
         }
+      }
     return upload16(out);
   }
   // fp32 packed [cout][cin] (one tap, one phase) -> [cin/32][cout][32] bf16 hi (conv_gemm_bf16dm)
