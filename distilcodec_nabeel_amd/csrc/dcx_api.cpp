@@ -580,8 +580,8 @@ int dcx_conv_forward(dcx_conv* c, int32_t gemm_mode, const float* x, int32_t bat
           return fail(h, DCX_ERR_HIP, "h3 input split (per row) failed: Cin must be 256, 512, 768, 1024 or a multiple of 32 below 256");
         xa.r.ash_row = ash;
       }
-      xa.h2 = true;
-    } else if (dcx::launch_split_planes(x, c->planes, (long long)batch * lin, c->w.cin, 0, s) != hipSuccess) {
+      xa.lay = dcx::LAYOUT_H2;
+    } else if (dcx::launch_split_planes(x, c->planes, (long long)batch * lin, c->w.cin, dcx::LAYOUT_PLANES, s) != hipSuccess) {
       return DCX_ERR_HIP;
     }
     xa.p = c->planes;

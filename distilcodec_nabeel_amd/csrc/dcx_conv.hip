@@ -156,14 +156,14 @@ __device__ __forceinline__ void splitk_epi4(const ConvParams& p, const float* __
   if (p.y) *reinterpret_cast<f32x4*>(p.y + o) = x;
   // h2 outputs (not produced in the split-K mode, which runs no h3 conv; kept consistent): the clip's
   // range scale (epilogue_lds); no maxima are recorded here
-  const float osc = (p.y6 && p.y_compact == 3) || (p.y6s && p.y6s_h2)
+  const float osc = (p.y6 && p.y_layout == LAYOUT_H2) || (p.y6s && p.ys_layout != LAYOUT_PLANES)
                         ? __builtin_ldexpf(1.0f, h2_shift(range_bound(p.yb, b))) : 1.0f;
   if (p.y6) {
-    unsigned short* y6 = p.y6 + ob * (p.y_compact == 1 ? 1 : p.y_compact >= 2 ? 2 : 3);
-    if (p.y_compact == 1) store_bf16x4(y6, orow, p.Cout, co, x[0], x[1], x[2], x[3]);
+    unsigned short* y6 = p.y6 + ob * layout_u16(p.y_layout);
+    if (p.y_layout == LAYOUT_BF16) store_bf16x4(y6, orow, p.Cout, co, x[0], x[1], x[2], x[3]);
     // unreachable (run_conv rejects layout 2); kept: removing it moved registers / scratch in other kernels
-    else if (p.y_compact == 2) store_hm4(y6, orow, p.Cout, co, x[0], x[1], x[2], x[3]);
-    else if (p.y_compact == 3) store_h2_4(y6, orow, p.Cout, co, x[0], x[1], x[2], x[3], osc);
+    else if ((int)p.y_layout == 2) store_hm4(y6, orow, p.Cout, co, x[0], x[1], x[2], x[3]);
+    else if (p.y_layout == LAYOUT_H2) store_h2_4(y6, orow, p.Cout, co, x[0], x[1], x[2], x[3], osc);
     else store_planes4(y6, orow, p.Cout, co, x[0], x[1], x[2], x[3]);
   }
   if (p.y2 || p.y6s) {
@@ -171,7 +171,7 @@ __device__ __forceinline__ void splitk_epi4(const ConvParams& p, const float* __
 #pragma unroll
     for (int e = 0; e < 4; ++e) sv[e] = silu_f(x[e]);
     if (p.y2) *reinterpret_cast<f32x4*>(p.y2 + o) = sv;
-    if (p.y6s && p.y6s_h2) store_h2_4(p.y6s + ob * 2, orow, p.Cout, co, sv[0], sv[1], sv[2], sv[3], osc);
+    if (p.y6s && p.ys_layout != LAYOUT_PLANES) store_h2_4(p.y6s + ob * 2, orow, p.Cout, co, sv[0], sv[1], sv[2], sv[3], osc);
     else if (p.y6s) store_planes4(p.y6s + ob * 3, orow, p.Cout, co, sv[0], sv[1], sv[2], sv[3]);
   }
 }
@@ -416,9 +416,9 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_bf16dm(const ConvParams p) {
   const int mt = wg / ntiles, nt = wg - mt * ntiles;
   const int q0 = mt * BM, co0 = nt * BN;
   const int nsteps = p.Cin / 32;
-  // input: planes (hi pieces at 48-byte strides, 6 bytes per element) or compact bf16 (x_compact:
+  // input: planes (hi pieces at 48-byte strides, 6 bytes per element) or compact bf16 (x_layout:
   // one contiguous 64-byte run per row and step); weights: planes w6 or compact wc likewise
-  const int xc = p.x_compact == 1 ? 1 : 3;
+  const int xc = p.x_layout == LAYOUT_BF16 ? 1 : 3;
   const int arow = p.ldx * 2 * xc, a_kq = 16 * xc, a_step = 64 * xc;
   const int row0 = q0 + p.in_base[ph];  // >= 0 for 1x1 convs; the descriptor covers the tile's rows
   const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
@@ -546,7 +546,7 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_bf16dm(const ConvParams p) {
 // only have to have drained by the next memory segment's wait.  Same MFMAs in the same order per
 // tile: the bits of conv_gemm_bf16dm<true> (tests/test_gpu_bf16.py::test_persistent_same_bits).
 // GELU launches finish from the LDS table of the bf16 GELU (gelu_lut_fill, filled while the first
-// steps' DMA is in flight).  Takes compact input and weights (x_compact == 1, wc), bf16 rounding,
+// steps' DMA is in flight).  Takes compact input and weights (LAYOUT_BF16, wc), bf16 rounding,
 // >= 3 K32 steps, one phase.
 // ---------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(512, 2) conv_gemm_bf16dp(const ConvParams p) {
@@ -839,7 +839,7 @@ bool bf16dm_takes(int cin, int cout, int lq, int ldx, int phases) {
 
 hipError_t launch_conv(const ConvParams& p, int batch, int phases, hipStream_t s, const char** kname) {
   if (p.Cin % BK || p.Cout % 32 || phases < 1 || phases > kMaxPhases) return hipErrorInvalidValue;
-  if (p.x_compact == 3) {  // h2 input: the h3 kernels only
+  if (p.x_layout == LAYOUT_H2) {  // h2 input: the h3 kernels only
     const int bn = x3dq_bn(p);
     if (!x3dq_ok(p, bn == 512 ? 256 : bn == 384 ? 128 : bn, bn >= 384)) return hipErrorInvalidValue;
     if (bn >= 384) return launch_x3dw(p, bn, batch, phases, s, kname);  // 384 x 128 (the C = 128 stage) or 256 x 256 tiles
@@ -879,7 +879,7 @@ hipError_t launch_conv(const ConvParams& p, int batch, int phases, hipStream_t s
     if (p.Cout % 128 == 0 && !h && !b1) return launch_x6pp<0>(p, batch, phases, s, kname);  // x6 1-tap
 #endif
     const bool dm_b1 = b1 && !h && p.taps == 1 && !p.fixed_tiles && in_base_nonneg(p) && bf16dm_takes(p.Cin, p.Cout, p.Lq, p.ldx, phases);
-    if (p.x_compact && (!dm_b1 || p.x_compact != 1)) return hipErrorInvalidValue;  // only conv_gemm_bf16dm reads it
+    if (p.x_layout != LAYOUT_PLANES && (!dm_b1 || p.x_layout != LAYOUT_BF16)) return hipErrorInvalidValue;  // only conv_gemm_bf16dm reads it
 #ifndef DCX_NO_BF16DM
     if (dm_b1) {
       ConvParams q = p;
@@ -891,11 +891,11 @@ hipError_t launch_conv(const ConvParams& p, int batch, int phases, hipStream_t s
       // output too (the VQ blocks' 1x1 convs) or a residual (pwconv2) it measured slower than the
       // staged epilogue, whose 16-byte stores cover 512 contiguous bytes of a row per instruction
       // (C3 bf16dm, A/B: pwconv1 only 52.5 ms, + the fp32-output convs 55.4, + pwconv2 56.6)
-      const bool reg = (p.epi == EPI_BIAS || p.epi == EPI_GELU) && p.y6 && p.y_compact == 1 && !p.y && !p.y2 &&
+      const bool reg = (p.epi == EPI_BIAS || p.epi == EPI_GELU) && p.y6 && p.y_layout == LAYOUT_BF16 && !p.y && !p.y2 &&
                        !p.y6s && p.mean_mode == MEAN_NONE && phases == 1 && p.out_mul == 1 && knobs(p).bf16_reg_epi;
       // the persistent form (one step stream across tiles) for compact operands; Knobs::bf16_persist = 0
       // (DCX_BF16_PERSIST=0) keeps conv_gemm_bf16dm<true> (A/B, same bits)
-      if (reg && p.x_compact == 1 && p.wc && p.round_bf16 && p.Cin / 32 >= 3 && p.Cout <= kBf16dpBiasMax &&
+      if (reg && p.x_layout == LAYOUT_BF16 && p.wc && p.round_bf16 && p.Cin / 32 >= 3 && p.Cout <= kBf16dpBiasMax &&
           (long long)std::min(256, p.Lq) * p.Cout * 2 < (1ll << 31) && knobs(p).bf16_persist) {
         if (kname) *kname = "conv_gemm_bf16dp<256,256,reg>";
         const long long tiles = (long long)grid.x;
@@ -987,17 +987,17 @@ static long long fill_group(ConvGroup& g, const ConvParams* ps, int n, int batch
 hipError_t launch_conv_group(const ConvParams* ps, int n, int batch, hipStream_t s, const char** kname) {
   if (n < 1 || n > kMaxGroup || batch < 1) return hipErrorInvalidValue;
   const int cout = ps[0].Cout;
-  const bool h3 = ps[0].x_compact == 3;  // h3 convs: conv_gemm_x3dw_group / x3dq_group (any tile count)
+  const bool h3 = ps[0].x_layout == LAYOUT_H2;  // h3 convs: conv_gemm_x3dw_group / x3dq_group (any tile count)
   const int bsel = h3 ? x3dq_bn(ps[0]) : 0;
   const int bn = h3 ? (bsel == 512 ? 256 : bsel == 384 ? 128 : bsel) : cout % 256 == 0 ? 256 : 128;
   const int bm = h3 ? (bsel == 512 ? 256 : bsel == 384 ? 384 : 32768 / bn) : 65536 / bn;
   for (int i = 0; i < n; ++i) {
     const ConvParams& p = ps[i];
     if (h3) {
-      if (p.Cout != cout || p.x_compact != 3 || p.taps < 3 || x3dq_bn(p) != bsel || !x3dq_ok(p, bn, bsel >= 384) ||
+      if (p.Cout != cout || p.x_layout != LAYOUT_H2 || p.taps < 3 || x3dq_bn(p) != bsel || !x3dq_ok(p, bn, bsel >= 384) ||
           (p.clip_len != nullptr) != (ps[0].clip_len != nullptr))
         return hipErrorNotSupported;
-    } else if (p.Cout != cout || cout % 128 || p.Cin % BK || !p.x6 || !p.w6 || p.nprod != 6 || p.x_compact ||
+    } else if (p.Cout != cout || cout % 128 || p.Cin % BK || !p.x6 || !p.w6 || p.nprod != 6 || p.x_layout != LAYOUT_PLANES ||
                p.taps < 3 || tap_span(p) == 0 || tap_span(p) > 64 || (p.Cin / BK) * p.taps % 2 ||
                !x6dm_ok(p, true, bn) || !big_tiles_pay(p, 1, bn)) {
       return hipErrorNotSupported;  // not one launch_conv would give to conv_gemm_x6dq<bn> (same bits either way)
@@ -1016,7 +1016,7 @@ hipError_t launch_conv_split_group(const ConvParams* ps, int n, int batch, hipSt
     const ConvParams& p = ps[i];
     const int S = std::max(1, p.ksplit);
     const int span = tap_span(p);
-    if (!p.x6 || !p.w6 || p.nprod != 6 || p.x_compact || p.Cout % 128 || p.Cin % BK || p.taps < 3 || span == 0 ||
+    if (!p.x6 || !p.w6 || p.nprod != 6 || p.x_layout != LAYOUT_PLANES || p.Cout % 128 || p.Cin % BK || p.taps < 3 || span == 0 ||
         span > 64 || (p.Cin / BK) * p.taps % 2 || (S > 1 && (p.kunit < 1 || (p.Cin / BK) % p.kunit ||
                                                             (p.Cin / BK) / p.kunit < S)))
       return hipErrorNotSupported;

@@ -214,7 +214,7 @@ struct EpiPre {
 template <int RROW>
 __device__ __forceinline__ EpiPre epi_range_pre(const ConvParams& p, const ConvParams& pr, int b) {
   EpiPre e{0, 0.f, false};
-  const bool h2o = (p.y6 && p.y_compact == 3) || (p.y6s && p.y6s_h2);
+  const bool h2o = (p.y6 && p.y_layout == LAYOUT_H2) || (p.y6s && p.ys_layout != LAYOUT_PLANES);
   const bool h2row = (RROW & 2) && h2o && pr.yb.rowwise;
   if (h2o && !h2row) {
     const float bnd = range_bound(pr.yb, b);
@@ -258,12 +258,12 @@ __device__ __forceinline__ void epilogue_lds(const ConvParams& p, const ConvPara
   const int wm = wave / WN, wn = wave % WN;
   const int lrow = lane & 31, rhalf = 4 * (lane >> 5);
   const long long ob = (long long)b * p.y_bstride;
-  unsigned short* y6 = p.y6 ? p.y6 + ob * (p.y_compact == 1 ? 1 : p.y_compact >= 2 ? 2 : 3) : nullptr;
-  unsigned short* y6s = p.y6s ? p.y6s + ob * (p.y6s_h2 ? 2 : 3) : nullptr;
+  unsigned short* y6 = p.y6 ? p.y6 + ob * layout_u16(p.y_layout) : nullptr;
+  unsigned short* y6s = p.y6s ? p.y6s + ob * (p.ys_layout != LAYOUT_PLANES ? 2 : 3) : nullptr;
   // h2 output range (dcx_kernels.h h2_shift): the clip's scale from its bound program, the same in
   // every workgroup of the clip, or (pr.yb.rowwise, one-tap convs) each row's from its own bound
   // (wave-uniform values moved to scalar registers: the accumulators still occupy most VGPRs here)
-  const bool h2o = (y6 && p.y_compact == 3) || (y6s && p.y6s_h2);
+  const bool h2o = (y6 && p.y_layout == LAYOUT_H2) || (y6s && p.ys_layout != LAYOUT_PLANES);
   constexpr bool RIN = RROW & 1, ROUT = RROW & 2;
   const bool h2row = ROUT && h2o && pr.yb.rowwise;
   int osh = 0;
@@ -424,7 +424,7 @@ __device__ __forceinline__ void epilogue_lds(const ConvParams& p, const ConvPara
               }
 #endif
               // a compact-only output rounds to bf16 in its store (the same RNE bits)
-              if (p.round_bf16 && (p.y || y6s || p.y2 || p.y_compact != 1)) x[h] = round_bf16x4(x[h]);
+              if (p.round_bf16 && (p.y || y6s || p.y2 || p.y_layout != LAYOUT_BF16)) x[h] = round_bf16x4(x[h]);
             } else {
 #pragma unroll
               for (int e = 0; e < 4; ++e) x[h][e] = gelu_f(x[h][e]);
@@ -489,10 +489,10 @@ __device__ __forceinline__ void epilogue_lds(const ConvParams& p, const ConvPara
 #pragma unroll
         for (int e = 0; e < 8; ++e) xv[e] = x[e >> 2][e & 3];
         if (y6) {
-          if (p.y_compact == 1) store_bf16x8(y6, orow, p.Cout, co, xv);
+          if (p.y_layout == LAYOUT_BF16) store_bf16x8(y6, orow, p.Cout, co, xv);
           // unreachable (run_conv rejects layout 2); kept: removing it moved registers / scratch in other kernels
-          else if (p.y_compact == 2) store_hm8(y6, orow, p.Cout, co, xv);
-          else if (p.y_compact == 3) store_h2_8<false>(y6, orow, p.Cout, co, xv, rsc);
+          else if ((int)p.y_layout == 2) store_hm8(y6, orow, p.Cout, co, xv);
+          else if (p.y_layout == LAYOUT_H2) store_h2_8<false>(y6, orow, p.Cout, co, xv, rsc);
           else store_planes8(y6, orow, p.Cout, co, xv);
         }
         if (p.y2 || y6s) {
@@ -504,16 +504,16 @@ __device__ __forceinline__ void epilogue_lds(const ConvParams& p, const ConvPara
             *reinterpret_cast<f32x4*>(p.y2 + o + 4) = f32x4{sv[4], sv[5], sv[6], sv[7]};
           }
           if (y6s) {
-            if (p.y6s_h2) store_h2_8<false>(y6s, orow, p.Cout, co, sv, rsc);
+            if (p.ys_layout != LAYOUT_PLANES) store_h2_8<false>(y6s, orow, p.Cout, co, sv, rsc);
             else store_planes8(y6s, orow, p.Cout, co, sv);
           }
         }
       } else {
         if (y6) {
-          if (p.y_compact == 1) store_bf16x4(y6, orow, p.Cout, co, x[0][0], x[0][1], x[0][2], x[0][3]);
+          if (p.y_layout == LAYOUT_BF16) store_bf16x4(y6, orow, p.Cout, co, x[0][0], x[0][1], x[0][2], x[0][3]);
           // unreachable (run_conv rejects layout 2); kept: removing it moved registers / scratch in other kernels
-          else if (p.y_compact == 2) store_hm4(y6, orow, p.Cout, co, x[0][0], x[0][1], x[0][2], x[0][3]);
-          else if (p.y_compact == 3) store_h2_4<false>(y6, orow, p.Cout, co, x[0][0], x[0][1], x[0][2], x[0][3], rsc);
+          else if ((int)p.y_layout == 2) store_hm4(y6, orow, p.Cout, co, x[0][0], x[0][1], x[0][2], x[0][3]);
+          else if (p.y_layout == LAYOUT_H2) store_h2_4<false>(y6, orow, p.Cout, co, x[0][0], x[0][1], x[0][2], x[0][3], rsc);
           else store_planes4(y6, orow, p.Cout, co, x[0][0], x[0][1], x[0][2], x[0][3]);
         }
         if (p.y2 || y6s) {
@@ -522,7 +522,7 @@ __device__ __forceinline__ void epilogue_lds(const ConvParams& p, const ConvPara
           for (int e = 0; e < 4; ++e) sv[e] = p.round_bf16 ? bf16_val(bf16_bits(silu_f(x[0][e]))) : silu_f(x[0][e]);
           if (p.y2) *reinterpret_cast<f32x4*>(p.y2 + o) = sv;
           if (y6s) {
-            if (p.y6s_h2) store_h2_4<false>(y6s, orow, p.Cout, co, sv[0], sv[1], sv[2], sv[3], rsc);
+            if (p.ys_layout != LAYOUT_PLANES) store_h2_4<false>(y6s, orow, p.Cout, co, sv[0], sv[1], sv[2], sv[3], rsc);
             else store_planes4(y6s, orow, p.Cout, co, sv[0], sv[1], sv[2], sv[3]);
           }
         }
@@ -569,9 +569,9 @@ __device__ __forceinline__ bool tile_dead(const ConvParams& p, const ConvParams&
 template <int BM, int BN, int NT>
 __device__ __forceinline__ void epilogue_dead(const ConvParams& p, const ConvParams& pr, int q0, int co0, int b, int ph) {
   const long long ob = (long long)b * p.y_bstride;
-  unsigned short* y6 = p.y6 ? p.y6 + ob * (p.y_compact == 1 ? 1 : p.y_compact >= 2 ? 2 : 3) : nullptr;
-  unsigned short* y6s = p.y6s ? p.y6s + ob * (p.y6s_h2 ? 2 : 3) : nullptr;
-  const bool h2o = (y6 && p.y_compact == 3) || (y6s && p.y6s_h2);
+  unsigned short* y6 = p.y6 ? p.y6 + ob * layout_u16(p.y_layout) : nullptr;
+  unsigned short* y6s = p.y6s ? p.y6s + ob * (p.ys_layout != LAYOUT_PLANES ? 2 : 3) : nullptr;
+  const bool h2o = (y6 && p.y_layout == LAYOUT_H2) || (y6s && p.ys_layout != LAYOUT_PLANES);
   if (h2o && threadIdx.x == 0) {
     const float bnd = range_bound(pr.yb, b);
     if (pr.y_ash) pr.y_ash[b] = h2_shift(bnd);
@@ -595,8 +595,8 @@ __device__ __forceinline__ void epilogue_dead(const ConvParams& p, const ConvPar
       *reinterpret_cast<f32x4*>(p.y + o + 4) = z4;
     }
     if (y6) {
-      if (p.y_compact == 1) store_bf16x8(y6, orow, p.Cout, co, z8);
-      else if (p.y_compact == 3) store_h2_8<false>(y6, orow, p.Cout, co, z8, 1.0f);
+      if (p.y_layout == LAYOUT_BF16) store_bf16x8(y6, orow, p.Cout, co, z8);
+      else if (p.y_layout == LAYOUT_H2) store_h2_8<false>(y6, orow, p.Cout, co, z8, 1.0f);
       else store_planes8(y6, orow, p.Cout, co, z8);
     }
     if (p.y2) {
@@ -604,7 +604,7 @@ __device__ __forceinline__ void epilogue_dead(const ConvParams& p, const ConvPar
       *reinterpret_cast<f32x4*>(p.y2 + o + 4) = z4;
     }
     if (y6s) {
-      if (p.y6s_h2) store_h2_8<false>(y6s, orow, p.Cout, co, z8, 1.0f);
+      if (p.ys_layout != LAYOUT_PLANES) store_h2_8<false>(y6s, orow, p.Cout, co, z8, 1.0f);
       else store_planes8(y6s, orow, p.Cout, co, z8);
     }
   }

@@ -452,11 +452,11 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_x3dw_group(const ConvGroup g
 }
 
 // Whether conv_gemm_x3dq<bn> (taps >= 3 with a halo) or conv_gemm_x3dm<bn> (one tap) takes an h3
-// conv (input in the h2 layout, x_compact == 3).
+// conv (input in LAYOUT_H2).
 // wide (conv_gemm_x3dw): taps >= 2 (its input buffer is free two segments before it is refilled)
 bool x3dq_ok(const ConvParams& p, int bn, bool wide) {
   const int span = (p.taps - 1) * (p.in_step < 0 ? -p.in_step : p.in_step);
-  if (!p.x6 || !p.w3 || p.x_compact != 3 || p.Cin % 32 || p.Cout % bn || p.ksplit > 1) return false;
+  if (!p.x6 || !p.w3 || p.x_layout != LAYOUT_H2 || p.Cin % 32 || p.Cout % bn || p.ksplit > 1) return false;
   const long long arow = (long long)p.ldx * 4;
   if ((long long)p.taps * p.Cin * p.Cout * 4 >= (1LL << 31)) return false;
   if (p.taps == 1) {  // per-tile descriptor: every phase's rows start at or after the tile's

@@ -503,7 +503,7 @@ __device__ __forceinline__ int b1_swz(int r) { return (0x1320 >> (((r >> 2) & 3)
 //
 // One v_mfma_f32_16x16x32_bf16 per 16 x 16 block and K32 step (lanes l >> 4 = 0..3 read the four
 // 16-byte pieces of 8 channels).  Both operands arrive as 64-byte runs per row / code and step:
-// x_pjt_in compact ([rows][CD] bf16, the project_in epilogue's y_compact == 1 output) and the
+// x_pjt_in compact ([rows][CD] bf16, the project_in epilogue's LAYOUT_BF16 output) and the
 // codebook as compact_pack (dcx_api.cpp) packs it ([CD/32][NC][32] bf16).  LDS images: 64-byte
 // rows, piece q in slot q ^ b1_swz(row), conflict-free for the four lane groups of a ds_read_b128.
 // Ring: NS slots of 16 + 16 KiB on the ping-pong schedule of vq_prefilter_dm generalised to NS slots
@@ -695,8 +695,8 @@ static bool vq_dm_ok(int ncodes, int dim) {
 // Code tile of the prefilter launch_vq_prefilter picks: 256 for vq_prefilter_b1 / vq_prefilter_dm, 128
 // for vq_prefilter_x3 (planes x_pjt_in where vq_prefilter_dm's limits fail).  (Routing searches of one
 // row panel, a streaming hop, to the 128-code tiles for twice the workgroups measured 1.55 -> 2.55 ms.)
-int vq_prefilter_ntiles(int ncodes, int dim, int x_layout) {
-  return ncodes / (x_layout == 1 || vq_dm_ok(ncodes, dim) ? 256 : 128);
+int vq_prefilter_ntiles(int ncodes, int dim, Layout x_layout) {
+  return ncodes / (x_layout == LAYOUT_BF16 || vq_dm_ok(ncodes, dim) ? 256 : 128);
 }
 
 // vq_prefilter_b1's ring depth (slots of 32 KiB; DCX_VQ_NS=3..5 in A/B builds)
@@ -714,12 +714,12 @@ bool vq_b1_takes(int ncodes, int dim) {
 // allowing 4 roundings per MFMA).  By Cauchy-Schwarz sum_k |x_k e_k| <= |x| max|e|, so each
 // approximate squared distance is within 2 * kVqPrefilterBound * |x| max|e| + 8 * 2^-24 (|x|^2 +
 // max|e|^2) of the exact one; vq_rescore_kernel uses that bound.
-// vq_prefilter_b1 (x_layout 1): x.e - x_h.e_h = x_r.e + x_h.d with
+// vq_prefilter_b1 (LAYOUT_BF16): x.e - x_h.e_h = x_r.e + x_h.d with
 // |x_r.e| <= |x_r| max|e| (the rescore's second term) and |x_h.d| <= |x_h| max|d| <= (1 + 2^-8)|x| dmax;
 // fp32 summation of the dim exact products, in whatever order the MFMAs add them, errs by at most
 // dim 2^-24 sum_k |x_h,k e_h,k| <= dim 2^-24 (1 + 2^-8)^2 |x| max|e|.
-double vq_prefilter_cx(int x_layout, int ncodes, int dim, float emax, float dmax) {
-  if (x_layout != 1 || !vq_b1_takes(ncodes, dim)) return (double)kVqPrefilterBound * emax;
+double vq_prefilter_cx(Layout x_layout, int ncodes, int dim, float emax, float dmax) {
+  if (x_layout != LAYOUT_BF16 || !vq_b1_takes(ncodes, dim)) return (double)kVqPrefilterBound * emax;
   return (1.0 + 0x1p-8) * (double)dmax + (double)dim * 0x1p-24 * (1.0 + 0x1p-6) * (double)emax;
 }
 
@@ -727,13 +727,13 @@ double vq_prefilter_cx(int x_layout, int ncodes, int dim, float emax, float dmax
 // with the planes codebook p.w6: vq_prefilter_dm where vq_dm_ok, else vq_prefilter_x3
 hipError_t launch_vq_prefilter(const ConvParams& p, int rows, bool x_bf16, hipStream_t s, const char** kname) {
   constexpr int BM = 256, BN = 128;
-  if (!p.x6 || !p.part_val2 || rows < 1 || (p.x_compact != 0 && p.x_compact != 1)) return hipErrorInvalidValue;
+  if (!p.x6 || !p.part_val2 || rows < 1 || (p.x_layout != LAYOUT_PLANES && p.x_layout != LAYOUT_BF16)) return hipErrorInvalidValue;
   ConvParams q = p;
   q.Lq = rows;
   q.Lin = rows;
   q.taps = 1;
   const dim3 grid256(vq_grid((rows + 255) / 256, p.Cout / 256));  // the 256 x 256 tiles of _b1 and _dm
-  if (p.x_compact == 1) {
+  if (p.x_layout == LAYOUT_BF16) {
     if (!p.wc || !vq_b1_takes(p.Cout, p.Cin)) return hipErrorInvalidValue;
     if (kname) *kname = "vq_prefilter_b1<256,256>";
     hipLaunchKernelGGL(vq_prefilter_b1<DCX_VQ_NS>, grid256, dim3(512), 0, s, q);

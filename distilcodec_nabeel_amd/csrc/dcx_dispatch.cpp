@@ -108,12 +108,11 @@ int conv_params(dcx_codec* h, const ConvW& w, const ConvCall& c, bool force_f32,
   p.round_bf16 = one;
   p.silu_in = c.silu_in;
   p.fixed_tiles = c.fixed_tiles ? 1 : 0;
-  p.x_compact = x6 && c.x.p && c.x.c1 ? 1 : 0;
-  p.y_compact = c.y6 ? c.y6c : 0;
-  p.y6s_h2 = c.y6s && c.y6s_h2 ? 1 : 0;
-  if (x6 && c.x.p && c.x.h2) {  // h3 arithmetic (conv_gemm_x3dq)
+  p.x_layout = x6 && c.x.p ? c.x.lay : LAYOUT_PLANES;
+  p.y_layout = c.y6 ? c.y_lay : LAYOUT_PLANES;
+  p.ys_layout = c.y6s ? c.ys_lay : LAYOUT_PLANES;
+  if (p.x_layout == LAYOUT_H2) {  // h3 arithmetic (conv_gemm_x3dq)
     if (!w.w3 || one) return fail(h, DCX_ERR_STATE, "internal: h2 input without h3 weights");
-    p.x_compact = 3;
     p.w3 = w.w3;
     p.w3_shift = w.w3_shift;
     p.x_ash = c.x.r.ash;
@@ -133,9 +132,11 @@ int conv_params(dcx_codec* h, const ConvW& w, const ConvCall& c, bool force_f32,
   p.kn = &h->knobs;
   // compact inputs only feed one-product GEMMs; a compact output (the RNE hi value) may also be written
   // in x6 mode (x_pjt_in for vq_prefilter_b1)
-  if (p.x_compact == 1 && !one) return fail(h, DCX_ERR_STATE, "internal: compact layout outside bf16 mode");
-  if (p.y_compact == 2) return fail(h, DCX_ERR_STATE, "internal: y6 layout 2 is unused");
-  if (p.y_compact == 3 && (!x6 || one)) return fail(h, DCX_ERR_STATE, "internal: h2 layout outside x6 mode");
+  for (Layout l : {p.x_layout, p.y_layout, p.ys_layout})
+    if (l != LAYOUT_PLANES && l != LAYOUT_BF16 && l != LAYOUT_H2) return fail(h, DCX_ERR_STATE, "internal: not a layout");
+  if (p.ys_layout == LAYOUT_BF16) return fail(h, DCX_ERR_STATE, "internal: y6s takes planes or h2 only");
+  if (p.x_layout == LAYOUT_BF16 && !one) return fail(h, DCX_ERR_STATE, "internal: compact layout outside bf16 mode");
+  if (p.y_layout == LAYOUT_H2 && (!x6 || one)) return fail(h, DCX_ERR_STATE, "internal: h2 layout outside x6 mode");
   return DCX_OK;
 }
 
@@ -144,6 +145,13 @@ int conv_params(dcx_codec* h, const ConvW& w, const ConvCall& c, bool force_f32,
 bool takes_compact(const dcx_codec* h, const ConvW& w, long long rows) {
   return h->compact && h->gemm_mode == DCX_GEMM_BF16 && w.wc && w.taps == 1 && w.phases == 1 && w.in_base[0] == 0 &&
          rows < (1LL << 31) && dcx::bf16dm_takes(w.cin, w.cout, (int)rows, w.cin, 1);
+}
+
+// The layout a producer writes for the one-tap conv w over `rows` rows: compact where conv_gemm_bf16dm
+// takes it, h2 where an h3 kernel does and the producer has the row ranges (h3_ranges), else planes.
+// takes_compact needs bf16 mode and takes_h3 x6 mode, so the two are never both true.
+Layout input_layout(const dcx_codec* h, const ConvW& w, long long rows, bool h3_ranges) {
+  return takes_compact(h, w, rows) ? LAYOUT_BF16 : h3_ranges && takes_h3(h, w) ? LAYOUT_H2 : LAYOUT_PLANES;
 }
 
 // Whether a generator conv with a tap halo (conv_pre, the ConvTs with Cout % 128 == 0) runs in h3
@@ -181,7 +189,7 @@ double conv_bytes(const ConvW& w, const ConvCall& c) {
 // (and so the low bits) then depends on S, i.e. on the tile count: the mode is opt-in and a clip
 // alone is not bit-equal to the same clip in a batch.
 static int split_factor(const dcx_codec* h, const ConvW& w, const ConvCall& c, const ConvParams& p) {
-  if (h->split_k < 2 || !h->split_buf || p.nprod != 6 || !p.w6 || !p.x6 || p.x_compact || w.cout % 128) return 1;
+  if (h->split_k < 2 || !h->split_buf || p.nprod != 6 || !p.w6 || !p.x6 || p.x_layout != LAYOUT_PLANES || w.cout % 128) return 1;
   const long long out = (long long)c.batch * c.Lq * w.out_mul * w.cout;
   if (out > kSplitMaxOut || (w.cin / 16) % (w.taps % 2 ? 2 : 1)) return 1;
   // tiles of the 256 x 128 kernels the slices run on (conv_gemm_x6pp / x6lm, whatever the big-tile
@@ -208,7 +216,7 @@ static ConvParams kslice_params(const ConvParams& p, const ConvW& w, int S, floa
   q.y6 = q.y6s = nullptr;
   q.epi = dcx::EPI_BIAS;
   q.mean_mode = dcx::MEAN_NONE;
-  q.y_compact = 0;
+  q.y_layout = LAYOUT_PLANES;
   q.round_bf16 = 0;
   q.y_ash = nullptr;  // the slices' clips are virtual; the split-K mode runs no h3 conv
   q.y_amax = nullptr;
@@ -407,17 +415,16 @@ ConvCall framed(CAct x, int B, int L, int C) {
 }
 
 
-// fp32 -> planes (or, with compact, bf16) for a tensor handed in by the caller (x6 / bf16 modes).
-// h2: the h2 layout instead (an h3 consumer; a planes tensor handed in with its fp32 copy is re-split),
-// range-scaled (dcx_kernels.h h2_shift) by the exact max of each clip (`clips` clips of rows / clips
-// rows: launch_h2_ranged, for the tap convs) or, with clips == 0, of each row (launch_h2_rows, for the
-// one-tap convs).  The scale follows from the values alone, so a tensor the fused pipeline would have
-// produced in h2 itself (a LayerNorm's row-scaled output) gets the same bits here.
-int ensure_planes(dcx_codec* h, CAct& a, long long rows, int C, Bump& ws, hipStream_t s, bool compact, bool h2,
-                  int clips, const int* lens) {
-  if (h2 && a.p && !a.h2 && a.f) a.p = nullptr;
+// fp32 -> the layout `want` for a tensor handed in by the caller (x6 / bf16 modes).  LAYOUT_H2 (an h3
+// consumer; a planes tensor handed in with its fp32 copy is re-split) is range-scaled (h2_shift) by the
+// exact max of each clip (`clips` clips of rows / clips rows: launch_h2_ranged, the tap convs) or, with
+// clips == 0, of each row (launch_h2_rows, the one-tap convs).  The scale follows from the values alone, so
+// a tensor the fused pipeline would have produced in h2 itself (a LayerNorm's output) gets the same bits.
+int ensure_planes(dcx_codec* h, CAct& a, long long rows, int C, Bump& ws, hipStream_t s, Layout want, int clips,
+                  const int* lens) {
+  const bool rh2 = want == LAYOUT_H2;
+  if (rh2 && a.p && a.lay != LAYOUT_H2 && a.f) a.p = nullptr;
   if (!x6_mode(h) || a.p) return DCX_OK;
-  const bool rh2 = h2 && !compact;
   unsigned short* p = ws.u16((size_t)rows * C * 3);
   float* am = rh2 && clips ? ws.f((size_t)clips) : nullptr;
   int* ash = rh2 ? ws.i((size_t)(clips ? clips : rows)) : nullptr;
@@ -436,30 +443,27 @@ int ensure_planes(dcx_codec* h, CAct& a, long long rows, int C, Bump& ws, hipStr
     a.r = Rng{};
     a.r.ash_row = ash;
   } else {
-    LAUNCH(h, s, "split_planes", 0, (compact ? 6.0 : 10.0) * rows * C,
-           dcx::launch_split_planes(a.f, p, rows, C, compact ? 1 : 0, s));
+    LAUNCH(h, s, "split_planes", 0, (want == LAYOUT_BF16 ? 6.0 : 10.0) * rows * C,
+           dcx::launch_split_planes(a.f, p, rows, C, want, s));
   }
   a.p = p;
-  a.c1 = compact;
-  a.h2 = rh2;
+  a.lay = want;
   return DCX_OK;
 }
 
-// ConvNeXtBlock in place on x [B][T][C] (fp32 residual stream); out6: optional planes (compact
-// with out6c = 1) of the block output for a following conv.  ln: [M][C], hid: [M][4C] conv-input
+// ConvNeXtBlock in place on x [B][T][C] (fp32 residual stream); out6: optional image (planes or
+// compact, out_lay) of the block output for a following conv.  ln: [M][C], hid: [M][4C] conv-input
 // scratch, written compact where their consumer takes it (bf16 mode), or in h2 with per-row ranges
 // (ln.row_ash / row_amax, hid.row_ash: the LayerNorm's exact row maxima, the hidden's rows bounded
 // by g1 max|LN row| + max|b1|; round 6).
 // rg: the rows are a ragged batch (B = 1, T = its total frames): the depthwise conv stays inside each clip.
 int run_block(dcx_codec* h, const BlockW& bw, float* x, unsigned short* out6, int B, int T, Act ln, Act hid,
-              hipStream_t s, int out6c, const dcx::RaggedSeg* rg) {
+              hipStream_t s, Layout out_lay, const dcx::RaggedSeg* rg) {
   const long long M = (long long)B * T;
   const int C = bw.C;
-  if (out6 && out6c == 3) return fail(h, DCX_ERR_STATE, "internal: a block output in h2 goes through launch_h2_rows");
-  ln.c1 = ln.p && takes_compact(h, bw.pw1, M);
-  hid.c1 = hid.p && takes_compact(h, bw.pw2, M);
-  ln.h2 = ln.p && ln.row_ash && ln.row_amax && takes_h3(h, bw.pw1);
-  hid.h2 = hid.p && hid.row_ash && takes_h3(h, bw.pw2);
+  if (out6 && out_lay == LAYOUT_H2) return fail(h, DCX_ERR_STATE, "internal: a block output in h2 goes through launch_h2_rows");
+  ln.lay = input_layout(h, bw.pw1, M, ln.row_ash && ln.row_amax);
+  hid.lay = input_layout(h, bw.pw2, M, hid.row_ash);
   ln.r = Rng{};
   hid.r = Rng{};
   ln.r.ash_row = ln.row_ash;
@@ -467,17 +471,17 @@ int run_block(dcx_codec* h, const BlockW& bw, float* x, unsigned short* out6, in
   if (rg) {
     if (B != 1 || T != rg->rows) return fail(h, DCX_ERR_STATE, "internal: ragged block rows");
     LAUNCH(h, s, "dwconv_ln_ragged", 14.0 * M * C, 8.0 * M * C,
-           dcx::launch_dwconv_ln_ragged(x, ln.f, ln.p, layout_of(ln), bw.dww, bw.dwb, bw.ln.w, bw.ln.b, *rg, C,
+           dcx::launch_dwconv_ln_ragged(x, ln.f, ln.p, ln.lay, bw.dww, bw.dwb, bw.ln.w, bw.ln.b, *rg, C,
                                         h->gemm_mode == DCX_GEMM_BF16 ? 1 : 0, &h->knobs, s, ln.row_ash, ln.row_amax));
   } else {
     LAUNCH(h, s, "dwconv_ln", 14.0 * M * C, 8.0 * M * C,
-           dcx::launch_dwconv_ln(x, ln.f, ln.p, layout_of(ln), bw.dww, bw.dwb, bw.ln.w, bw.ln.b, B, T, C,
+           dcx::launch_dwconv_ln(x, ln.f, ln.p, ln.lay, bw.dww, bw.dwb, bw.ln.w, bw.ln.b, B, T, C,
                                  h->gemm_mode == DCX_GEMM_BF16 ? 1 : 0, &h->knobs, s, ln.row_ash, ln.row_amax));
   }
   ConvCall c1 = pointwise(ln, M);
   c1.out_to(hid);
   c1.epi = dcx::EPI_GELU;
-  if (hid.h2) {  // |GELU(v)| <= |v| <= g1 max|LN row| + max|b1|
+  if (hid.p && hid.lay == LAYOUT_H2) {  // |GELU(v)| <= |v| <= g1 max|LN row| + max|b1|
     c1.yb = prog_conv_rows(bw.pw1, ln.row_amax);
     c1.y_ash = hid.row_ash;
   }
@@ -485,7 +489,7 @@ int run_block(dcx_codec* h, const BlockW& bw, float* x, unsigned short* out6, in
   ConvCall c2 = pointwise(hid, M);
   c2.y = x;
   c2.y6 = out6;
-  c2.y6c = out6 ? out6c : 0;  // 0 planes, 1 compact
+  c2.y_lay = out_lay;
   c2.res = x;
   c2.gamma = bw.gamma;
   c2.epi = dcx::EPI_GAMMA_RES;
@@ -494,13 +498,13 @@ int run_block(dcx_codec* h, const BlockW& bw, float* x, unsigned short* out6, in
 }
 
 // channels-first LayerNorm; bf16_in: its input is a bf16 tensor under the reference's autocast (the
-// stem's, in bf16 mode), so its mean and differences are bf16 (ln_rows form 2).  An h2 output (y.h2)
+// stem's, in bf16 mode), so its mean and differences are bf16 (ln_rows form 2).  An h2 output
 // is scaled per row by its exact max (y.row_ash receives the shifts, y.row_amax the maxima if set).
 int run_ln(dcx_codec* h, const LnW& l, const float* x, Act y, long long rows, hipStream_t s, bool bf16_in) {
   const int form = bf16_in && h->gemm_mode == DCX_GEMM_BF16 ? 2 : 1;
-  if (y.p && y.h2 && !y.row_ash) return fail(h, DCX_ERR_STATE, "internal: h2 LayerNorm output without row ranges");
+  if (y.p && y.lay == LAYOUT_H2 && !y.row_ash) return fail(h, DCX_ERR_STATE, "internal: h2 LayerNorm output without row ranges");
   LAUNCH(h, s, "ln_rows", 8.0 * rows * l.C, 8.0 * rows * l.C,
-         dcx::launch_ln_rows(x, y.f, y.p, y.p ? layout_of(y) : 0, l.w, l.b, rows, l.C, 1e-6f, form, s,
+         dcx::launch_ln_rows(x, y.f, y.p, y.lay, l.w, l.b, rows, l.C, 1e-6f, form, s,
                              y.row_ash, y.row_amax));
   return DCX_OK;
 }

@@ -141,7 +141,7 @@ int run_parallel_block(dcx_codec* h, int i, int B, int Lo, const PBlockBufs& b, 
       w1[rb] = &h->res[i][rb][ci][0];
       c1[rb].yb = prog_conv(*w1[rb], in1[rb]);
       c1[rb].y_amax = ra.amax();
-      c1[rb].y_ash = b.Tb_in[rb].h2 ? ra.ash() : nullptr;
+      c1[rb].y_ash = b.Tb_in[rb].lay == LAYOUT_H2 ? ra.ash() : nullptr;
       tr[rb].ash = c1[rb].y_ash;
       tr[rb].amax = c1[rb].y_amax;
     }
@@ -164,7 +164,7 @@ int run_parallel_block(dcx_codec* h, int i, int B, int Lo, const PBlockBufs& b, 
         prog_add(c2[rb].yb, 1.0f, st[rb]);
         prog_add(c2[rb].yb, w2[rb]->g_abs, tr[rb]);
         c2[rb].y_amax = ra.amax();
-        c2[rb].y_ash = !silu_on_load && b.RS[rb].h2 ? ra.ash() : nullptr;
+        c2[rb].y_ash = !silu_on_load && b.RS[rb].lay == LAYOUT_H2 ? ra.ash() : nullptr;
       }
       RUN(run_conv_group(h, w2, c2, c.n_res, s));
       for (int rb = 0; rb < c.n_res; ++rb) {
@@ -259,7 +259,7 @@ int stage_generate(dcx_codec* h, CAct z, int B, int T, float* wav, Bump& ws, hip
       return fail(h, DCX_ERR_INVALID_ARG, "ragged decode needs conv_pre in h3 arithmetic (DCX_H3=0: z would be split unbounded)");
   }
   // z in conv_pre's h2 form, range-scaled by each clip's exact max (the fused pipeline's z as well)
-  RUN(ensure_planes(h, z, (long long)B * T, c.vq_dim, ws, s, false, takes_h3_conv(h, h->conv_pre, T), B, lens));
+  RUN(ensure_planes(h, z, (long long)B * T, c.vq_dim, ws, s, h2_if(takes_h3_conv(h, h->conv_pre, T)), B, lens));
   const size_t per = (size_t)B * T * max_gen_width(c);
   // The ParallelBlock's ResBlocks are independent until the mean, so each keeps its own state and
   // the convs of one dilation index run as one grouped launch (run_conv_group).
@@ -295,11 +295,11 @@ int stage_generate(dcx_codec* h, CAct z, int B, int T, float* wav, Bump& ws, hip
     ConvCall cc = framed(z, B, T, c.vq_dim);
     cc.ragged(lens, T);
     Act S0 = S;
-    S0.h2 = S.p && takes_h3_conv(h, h->ups[0], T);
+    S0.lay = h2_if(S.p && takes_h3_conv(h, h->ups[0], T));
     cc.silu_to(S0);
     cc.yb = prog_conv(h->conv_pre, z.r);
     cc.y_amax = ra.amax();
-    cc.y_ash = S0.h2 ? ra.ash() : nullptr;
+    cc.y_ash = S0.lay == LAYOUT_H2 ? ra.ash() : nullptr;
     RUN(run_conv(h, h->conv_pre, cc, s));
     S.r = Rng{cc.y_ash, 0, cc.y_amax, 0.f};
   }
@@ -308,7 +308,7 @@ int stage_generate(dcx_codec* h, CAct z, int B, int T, float* wav, Bump& ws, hip
     const int Co = up.cout, Lo = L * c.up_rates[i];
     const ConvW& rconv = h->res[i][0][0][0];  // every ResBlock conv of the stage has Cin = Cout = Co
     Act S_i = in_form(S, up);
-    S_i.h2 = S_i.p && takes_h3_conv(h, up, L);  // as conv_pre / the previous stage's mean epilogue wrote it
+    S_i.lay = h2_if(S_i.p && takes_h3_conv(h, up, L));  // as conv_pre / the previous stage's mean epilogue wrote it
     Act XS_i = in_form(XS, rconv);
     Act RS_i[NR], Tb_i[NR];
     for (int rb = 0; rb < c.n_res; ++rb) {
@@ -319,8 +319,8 @@ int stage_generate(dcx_codec* h, CAct z, int B, int T, float* wav, Bump& ws, hip
     // silu(X) and silu(R) are never written (7 activation tensors per stage less HBM traffic)
     const bool silu_on_load = x6_mode(h) && f32_input_ok(rconv);
     if (h3_stage(h, i, Lo)) {  // the ResBlock convs' inputs in the h2 layout (conv_gemm_x3dq)
-      XS_i.h2 = true;
-      for (int rb = 0; rb < c.n_res; ++rb) RS_i[rb].h2 = Tb_i[rb].h2 = true;
+      XS_i.lay = LAYOUT_H2;
+      for (int rb = 0; rb < c.n_res; ++rb) RS_i[rb].lay = Tb_i[rb].lay = LAYOUT_H2;
     }
     float* amax_X = ra.amax();
     {
@@ -330,7 +330,7 @@ int stage_generate(dcx_codec* h, CAct z, int B, int T, float* wav, Bump& ws, hip
       if (!silu_on_load) cc.silu_to(XS_i);
       cc.yb = prog_conv(up, S_i.r);
       cc.y_amax = amax_X;
-      cc.y_ash = !silu_on_load && XS_i.h2 ? ra.ash() : nullptr;
+      cc.y_ash = !silu_on_load && XS_i.lay == LAYOUT_H2 ? ra.ash() : nullptr;
       RUN(run_conv(h, up, cc, s));
       XS_i.r = Rng{cc.y_ash, 0, amax_X, 0.f};
     }
@@ -351,9 +351,9 @@ int stage_generate(dcx_codec* h, CAct z, int B, int T, float* wav, Bump& ws, hip
     pb.frames_max = T;
     if (!pb.last) {
       pb.next = in_form(S, h->ups[i + 1]);
-      pb.next.h2 = pb.next.p && takes_h3_conv(h, h->ups[i + 1], Lo);
+      pb.next.lay = h2_if(pb.next.p && takes_h3_conv(h, h->ups[i + 1], Lo));
       pb.next_amax = ra.amax();
-      pb.next_ash = pb.next.h2 ? ra.ash() : nullptr;
+      pb.next_ash = pb.next.lay == LAYOUT_H2 ? ra.ash() : nullptr;
     }
     if (!ra.ok()) return fail(h, DCX_ERR_STATE, "internal: h3 range slots exhausted");
     RUN(run_parallel_block(h, i, B, Lo, pb, s));

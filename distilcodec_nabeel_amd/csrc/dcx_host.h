@@ -259,11 +259,8 @@ inline float bf16_f(unsigned short b) {
   return f;
 }
 
-// An activation tensor [rows][C]: fp32 and/or x6 planes ([rows][C/8][3][8] bf16, dcx_planes.h).
-// c1: p holds the compact bf16 layout ([rows][C] hi only; consumers conv_gemm_bf16dm in bf16 mode,
-// vq_prefilter_b1 in either mode) instead of planes.
-// h2: p holds the fp16 "h2" layout ([rows][C/32][8][8] h and l; the h3 generator arithmetic,
-// consumer conv_gemm_x3dq).
+// An activation tensor [rows][C]: fp32 (f) and/or its 16-bit image (p) in the layout lay
+// (dcx_kernels.h Layout).
 // Range of a tensor (round 6, dcx_kernels.h h2_shift): in the h2 layout it holds x * 2^ash[clip]
 // (ash null: ash_c for every clip); |x| <= max(amax[clip], amax_f) (amax null: amax_f), the input
 // term of its consumers' bound programs.
@@ -278,25 +275,23 @@ struct Rng {
 struct Act {
   float* f = nullptr;
   unsigned short* p = nullptr;
-  bool c1 = false;
-  bool h2 = false;
+  Layout lay = LAYOUT_PLANES;
   Rng r;
   // per-row range buffers an h2 producer fills for a one-tap consumer (round 6): the shift and (for
   // LayerNorm outputs) the max |.| of each row
   int* row_ash = nullptr;
   float* row_amax = nullptr;
 };
-// layout code of a.p (ConvParams::x_compact / y_compact, the LayerNorm launchers): 0 planes, 1 compact bf16, 3 h2
-inline int layout_of(const Act& a) { return a.c1 ? 1 : a.h2 ? 3 : 0; }
+// the layout of a tensor whose consumer runs in h3 arithmetic (h2) or in x6 (planes)
+inline Layout h2_if(bool h3) { return h3 ? LAYOUT_H2 : LAYOUT_PLANES; }
 struct CAct {
   const float* f = nullptr;
   const unsigned short* p = nullptr;
-  bool c1 = false;
-  bool h2 = false;
+  Layout lay = LAYOUT_PLANES;
   Rng r;
   CAct() = default;
-  CAct(const float* f_, const unsigned short* p_, bool c1_ = false) : f(f_), p(p_), c1(c1_) {}
-  CAct(const Act& a) : f(a.f), p(a.p), c1(a.c1), h2(a.h2), r(a.r) {}
+  CAct(const float* f_, const unsigned short* p_, Layout lay_ = LAYOUT_PLANES) : f(f_), p(p_), lay(lay_) {}
+  CAct(const Act& a) : f(a.f), p(a.p), lay(a.lay), r(a.r) {}
 };
 
 // planes layout for every GEMM operand (x6 and bf16 modes)
@@ -308,10 +303,9 @@ struct ConvCall {
   int batch, Lin, Lq, ldx;
   float* y = nullptr;            // v
   float* y2 = nullptr;           // silu(v), fp32
-  unsigned short* y6 = nullptr;  // planes of v
-  unsigned short* y6s = nullptr; // planes of silu(v)
-  bool y6s_h2 = false;           // y6s in the h2 layout
-  int y6c = 0;                   // y6 layout (ConvParams::y_compact): 0 planes, 1 compact bf16, 3 h2 (2 unused)
+  unsigned short* y6 = nullptr;  // image of v, in y_lay (out_to)
+  unsigned short* y6s = nullptr; // image of silu(v), in ys_lay: planes or h2 (silu_to)
+  Layout y_lay = LAYOUT_PLANES, ys_lay = LAYOUT_PLANES;
   float* macc = nullptr;
   const float* res = nullptr;
   const float* gamma = nullptr;
@@ -335,9 +329,9 @@ struct ConvCall {
   void silu_to(const Act& a) {
     y2 = a.f;
     y6s = a.p;
-    y6s_h2 = a.h2;
+    ys_lay = a.lay;
   }
-  void out_to(const Act& a) { y = a.f; y6 = a.p; y6c = layout_of(a); }
+  void out_to(const Act& a) { y = a.f; y6 = a.p; y_lay = a.lay; }
 };
 
 // Per-call range slots of the generator (round 6): measured per-clip maxima and h2 shifts, [slot][clip],
@@ -410,6 +404,7 @@ int conv_params(dcx_codec* h, const ConvW& w, const ConvCall& c, bool force_f32,
 bool takes_compact(const dcx_codec* h, const ConvW& w, long long rows);
 bool takes_h3_conv(const dcx_codec* h, const ConvW& w, long long rows);
 bool takes_h3(const dcx_codec* h, const ConvW& w);
+Layout input_layout(const dcx_codec* h, const ConvW& w, long long rows, bool h3_ranges = true);
 bool h3_rows_ok(long long rows, int cin);
 double conv_flops(const ConvW& w, const ConvCall& c);
 double conv_bytes(const ConvW& w, const ConvCall& c);
@@ -419,10 +414,10 @@ int run_conv_group_split(dcx_codec* h, const ConvW* const* w, const ConvCall* c,
 int run_conv_group(dcx_codec* h, const ConvW* const* w, const ConvCall* c, int n, hipStream_t s);
 ConvCall pointwise(CAct x, long long rows);
 ConvCall framed(CAct x, int B, int L, int C);
-int ensure_planes(dcx_codec* h, CAct& a, long long rows, int C, Bump& ws, hipStream_t s, bool compact = false,
-                  bool h2 = false, int clips = 0, const int* lens = nullptr);
+int ensure_planes(dcx_codec* h, CAct& a, long long rows, int C, Bump& ws, hipStream_t s,
+                  Layout want = LAYOUT_PLANES, int clips = 0, const int* lens = nullptr);
 int run_block(dcx_codec* h, const BlockW& bw, float* x, unsigned short* out6, int B, int T, Act ln, Act hid,
-              hipStream_t s, int out6c = 0, const dcx::RaggedSeg* rg = nullptr);
+              hipStream_t s, Layout out_lay = LAYOUT_PLANES, const dcx::RaggedSeg* rg = nullptr);
 int run_ln(dcx_codec* h, const LnW& l, const float* x, Act y, long long rows, hipStream_t s, bool bf16_in = false);
 void row_ranges(dcx_codec* h, Bump& ws, long long M, Act& ln, Act& hid);
 
@@ -433,9 +428,9 @@ int stage_mel(dcx_codec* h, const float* audio, int B, int64_t n, Act mel, Bump&
 // fork: the call may put its second half-batch on the side stream (false inside a half of stage_encode_decode)
 int stage_encode(dcx_codec* h, CAct mel, int B, int T, Act feat, Bump& ws, hipStream_t s,
                  const dcx::RaggedSeg* rg = nullptr, bool fork = true);
-int vq_xlayout(const dcx_codec* h);
+Layout vq_xlayout(const dcx_codec* h);
 VqScratch vq_scratch(const dcx_codec* h, Bump& ws, long long M, int ntiles, bool x6);
-int run_vq_search(dcx_codec* h, const float* P, const unsigned short* P6, int xl, long long M, const VqScratch& v,
+int run_vq_search(dcx_codec* h, const float* P, const unsigned short* P6, Layout xl, long long M, const VqScratch& v,
                   int ntiles, int32_t* codes, hipStream_t s);
 int stage_vq_encode(dcx_codec* h, CAct feat, int B, int T, int32_t* codes, float* pin, float* fup, float* quant,
                     Bump& ws, hipStream_t s, const dcx::RaggedSeg* rg = nullptr);

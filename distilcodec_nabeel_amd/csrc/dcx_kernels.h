@@ -20,6 +20,19 @@ enum Mean : int { MEAN_NONE = 0, MEAN_FIRST = 1, MEAN_MID = 2, MEAN_LAST = 3 };
 
 constexpr int kMaxPhases = 8;
 
+// Layout of the 16-bit image of an activation tensor [rows][C] (dcx_planes.h has the stores).  It decides
+// the kernel family that may read the buffer, the bytes per element, and whether range shifts travel with it:
+//  * LAYOUT_PLANES: three bf16 planes per 8 channels, [rows][C/8][plane 3][8], 6 bytes per element; hi +
+//    mid + lo reproduces the fp32 value to 2^-27.  Read by the x6 kernels (hi only: the bf16-mode ones).
+//  * LAYOUT_BF16 ("compact"): [rows][C] bf16, the hi plane alone, 2 bytes per element.  Read by
+//    conv_gemm_bf16dm / bf16dp (bf16 mode only) and by vq_prefilter_b1 (x_pjt_in, either mode).
+//  * LAYOUT_H2: fp16 h = fp16(y), l = fp16(y - h) per 32 channels, [rows][C/32][8][8], 4 bytes per element,
+//    y = x * 2^shift, the shift per clip or row (h2_shift).  Read by the h3 kernels (x6 mode only).
+// The values are the ones the kernels compare against (2 was the retired "hm" layout).
+enum Layout : int { LAYOUT_PLANES = 0, LAYOUT_BF16 = 1, LAYOUT_H2 = 3 };
+// 16-bit words per element (>= 2: the epilogues keep layout 2's unreachable arm, profiles/layout_enum_ab.md)
+__host__ __device__ constexpr int layout_u16(Layout l) { return l == LAYOUT_BF16 ? 1 : (int)l >= 2 ? 2 : 3; }
+
 // ---- h3 activation range (round 6) ------------------------------------------------------------
 // An h2 pair (h = fp16(y), l = fp16(y - h)) carries 22 significant bits only while |y| lies in
 // [2^-3, 2^16): below, l goes subnormal (an absolute floor of 2^-25), above, fp16 saturates.  Every
@@ -136,11 +149,10 @@ struct Knobs {
 // out[b][q*out_mul + phase][co] = epi( sum_{m<taps} sum_{ci<Cin} x[b][q + in_base[phase] + m*in_step][ci]
 //                                       * w[phase][co][m*Cin + ci] + bias[co] )
 // Rows of x outside [0, Lin) read as zero (zero padding).  Channels-last everywhere.
-// x6 activations ("planes"): an fp32 tensor [rows][C] held as three bf16 planes interleaved per
-// 8 channels, [rows][C/8][plane 3][8] (6 bytes/element); hi + mid + lo reproduces x to 2^-27.
+// x6 / y6 / y6s: 16-bit images of fp32 tensors [rows][C], in x_layout / y_layout / ys_layout.
 struct ConvParams {
   const float* x;
-  const unsigned short* x6;     // x6 mode input planes (row stride 3*ldx elements)
+  const unsigned short* x6;     // x6 mode input image (planes: row stride 3*ldx elements)
   const float* w;               // fp32 weights [phase][Cout][taps*Cin]
   const unsigned short* w6;     // if set: x6 mode, bf16 split weights [phase][tap][Cin/16][Cout][2][3][8]
   const float* bias;   // may be null
@@ -149,8 +161,8 @@ struct ConvParams {
   float* y;            // v (may be null)
   float* y2;           // silu(v) (may be null)
   float* macc;         // mean accumulator, layout of y (MEAN_* != NONE)
-  unsigned short* y6;  // planes of v (may be null; needs ldy == Cout)
-  unsigned short* y6s; // planes of silu(v) (may be null)
+  unsigned short* y6;  // image of v (may be null; needs ldy == Cout)
+  unsigned short* y6s; // image of silu(v) (may be null)
   long long x_bstride;      // elements between clips in x
   long long y_bstride;      // elements between clips in y / y2 / res / macc
   long long w_phase_stride; // elements between phases in w
@@ -172,12 +184,8 @@ struct ConvParams {
   // fp32-input (AF32) kernels: apply silu to the input while staging (the producer then writes
   // only the fp32 tensor, not its silu as well)
   int silu_in;
-  // Layouts other than planes for x6 / y6 (dcx_planes.h), 0 = planes:
-  //   1 = compact bf16 ([rows][C], hi plane only; read by conv_gemm_bf16dm (bf16 mode) and
-  //       vq_prefilter_b1 (x_pjt_in, either mode); ldy == Cout);
-  //   3 = "h2" ([rows][C/32][8][8] fp16 h and l per 32 channels; read by the h3 kernels).
-  // 2 is unused.
-  int x_compact, y_compact;
+  // layouts of x6 and y6 (LAYOUT_BF16 output: ldy == Cout)
+  Layout x_layout, y_layout;
   // bf16-mode 1x1 weights as [phase][Cin/32][Cout][32] bf16 (hi only; conv_gemm_bf16dm), or null;
   // for vq_prefilter_b1: the codebook in the same layout (compact_pack, dcx_api.cpp).
   const unsigned short* wc;
@@ -198,15 +206,14 @@ struct ConvParams {
   // tiles where big_tiles_pay would take the 64K-output ones (a ragged batch's one-tap DFT and stem:
   // a clip's bits must not depend on how many rows share its launch)
   int fixed_tiles;
-  // h3 arithmetic (conv_gemm_x3dq, x_compact == 3: the input in the fp16 "h2" layout of
-  // dcx_planes.h): weights fp16 h / l of w * 2^w3_shift, steps [phase][tap][Cin/32] of Cout * 128
-  // bytes, each in the order of dcx_w3_layout.h (w3_offset)
+  // h3 arithmetic (conv_gemm_x3dq, x_layout == LAYOUT_H2): weights fp16 h / l of w * 2^w3_shift, steps
+  // [phase][tap][Cin/32] of Cout * 128 bytes, each in the order of dcx_w3_layout.h (w3_offset)
   const unsigned short* w3;
   int w3_shift;
-  // y6s in the h2 layout instead of planes (the input of a following h3 conv)
-  int y6s_h2;
+  // layout of y6s: planes, or h2 (the input of a following h3 conv); never compact
+  Layout ys_layout;
   // h3 activation range (round 6, see h2_shift): the h2 input holds x * 2^x_ash[clip] (x_ash null:
-  // x_ash_c for every clip); an h2 output (y6 with y_compact == 3, or y6s with y6s_h2) is written as
+  // x_ash_c for every clip); an h2 output (y6 or y6s in LAYOUT_H2) is written as
   // v * 2^h2_shift(yb(clip)) and that shift stored to y_ash[clip] (may be null); y_amax (may be null)
   // receives the per-clip max |v| of the epilogue's final value v (atomicMax on the fp32 bits);
   // rflag (may be null) the RangeFlag bits
@@ -317,12 +324,11 @@ hipError_t launch_splitk_epilogue_group(const ConvParams* ps, const float* const
                                         const long long* strides, int n, int batch, bool chain, hipStream_t s);
 hipError_t launch_vq_argmin(const ConvParams& p, int rows, hipStream_t s, const char** kname);
 int vq_argmin_ntiles(int ncodes);
-// per-row partial count of the prefilter launch_vq_prefilter runs with x_pjt_in in layout x_layout
-// (ConvParams::x_compact: 0 planes, 1 compact bf16)
-int vq_prefilter_ntiles(int ncodes, int dim, int x_layout);
+// per-row partial count of the prefilter launch_vq_prefilter runs with x_pjt_in in x_layout (planes / compact)
+int vq_prefilter_ntiles(int ncodes, int dim, Layout x_layout);
 // VQ search, x6 / bf16 mode: prefilter (approximate squared distances, per-tile top 2) ...
-// p.x_compact == 1 with p.wc the [CD/32][NC][32] bf16 hi codebook: vq_prefilter_b1 (one product,
-// both modes; vq_b1_takes).  p.x_compact == 0 (planes, p.w6 the planes codebook): vq_prefilter_dm
+// p.x_layout == LAYOUT_BF16 with p.wc the [CD/32][NC][32] bf16 hi codebook: vq_prefilter_b1 (one product,
+// both modes; vq_b1_takes).  LAYOUT_PLANES (p.w6 the planes codebook): vq_prefilter_dm
 // or, where its shape limits fail, vq_prefilter_x3 (three products); x_bf16: the rows of x are bf16
 // values (mid and lo planes zero), which drops the mid*hi product.
 hipError_t launch_vq_prefilter(const ConvParams& p, int rows, bool x_bf16, hipStream_t s, const char** kname);
@@ -332,7 +338,7 @@ bool vq_b1_takes(int ncodes, int dim);
 constexpr float kVqPrefilterBound = 2.5e-4f;
 // Coefficient cx of |x| in the half-width of the prefilter's error for x_pjt_in in layout x_layout
 // (vq_rescore: bound = 2 (cx |x| + max|e| |x_r|) + 8 2^-24 (|x|^2 + max|e|^2)); dmax = max |e - bf16(e)|.
-double vq_prefilter_cx(int x_layout, int ncodes, int dim, float emax, float dmax);
+double vq_prefilter_cx(Layout x_layout, int ncodes, int dim, float emax, float dmax);
 // vq_rescore arguments.  part_*: the prefilter's [rows][ntiles] partials; x: x_pjt_in fp32
 // [rows][dim]; x2 / x2d: |x|^2 per row (row_sqnorm, fp32 / fp64); xr2 (optional): |x - bf16(x)|^2,
 // required for vq_prefilter_b1's bound; e2d: |e|^2 per code in fp64; cx / emax / e2max: the bound
@@ -367,16 +373,16 @@ hipError_t launch_vq_reduce(const float* part_val, const int* part_idx, int rows
 // x2 (fp32) and optionally x2d (fp64) |x|^2, xr2 |x - bf16(x)|^2 per row; zero_me (optional) set to 0
 hipError_t launch_row_sqnorm(const float* x, long long rows, int C, float* out, double* x2d, float* xr2,
                              unsigned long long* zero_me, hipStream_t s);
-// y6c: y6 in the compact bf16 layout instead of planes; channels_first_form: 0 F.layer_norm, 1 the
+// lay: the layout of y6; channels_first_form: 0 F.layer_norm, 1 the
 // reference's channels_first LayerNorm, 2 the latter on a bf16 input under CUDA autocast.
-// An h2 output (y6c == 3) is scaled per row by 2^h2_shift(the row's max |output|), that shift stored
+// An h2 output is scaled per row by 2^h2_shift(the row's max |output|), that shift stored
 // to ash_row[row] (required) and the max to amax_row[row] (may be null)
-hipError_t launch_ln_rows(const float* x, float* y, unsigned short* y6, int y6c, const float* w, const float* b,
+hipError_t launch_ln_rows(const float* x, float* y, unsigned short* y6, Layout lay, const float* w, const float* b,
                           long long rows, int C, float eps, int channels_first_form, hipStream_t s,
                           int* ash_row = nullptr, float* amax_row = nullptr);
 // bf16: the reference's CUDA autocast (DCX_GEMM_BF16): input, taps and bias rounded to bf16, the
 // depthwise conv's result rounded to bf16, then the fp32 F.layer_norm
-hipError_t launch_dwconv_ln(const float* x, float* y, unsigned short* y6, int y6c, const float* dww, const float* dwb,
+hipError_t launch_dwconv_ln(const float* x, float* y, unsigned short* y6, Layout lay, const float* dww, const float* dwb,
                             const float* lnw, const float* lnb, int batch, int L, int C, int bf16, const Knobs* kn,
                             hipStream_t s, int* ash_row = nullptr, float* amax_row = nullptr);
 // fp32 [rows][C] -> h2, each row scaled by 2^h2_shift(its max |x|), the shift to ash_row[row] (the
@@ -424,18 +430,18 @@ hipError_t launch_ragged_frames(const float* audio, const RaggedSeg& g, float* f
 // of [rows][taps * C] (fp32, planes)
 hipError_t launch_ragged_unfold(const void* x, void* y, const RaggedSeg& g, int row_bytes, int taps, hipStream_t s);
 // launch_dwconv_ln on a ragged batch: taps outside the row's own clip are dropped
-hipError_t launch_dwconv_ln_ragged(const float* x, float* y, unsigned short* y6, int y6c, const float* dww,
+hipError_t launch_dwconv_ln_ragged(const float* x, float* y, unsigned short* y6, Layout lay, const float* dww,
                                    const float* dwb, const float* lnw, const float* lnb, const RaggedSeg& g, int C,
                                    int bf16, const Knobs* kn, hipStream_t s, int* ash_row = nullptr,
                                    float* amax_row = nullptr);
 hipError_t launch_frame_pad(const float* audio, float* frames, unsigned short* frames6, int batch, long long n, int rows,
                             int hop, int pad_left, hipStream_t s);
-// h2: y6 in the h2 layout (dcx_planes.h) instead of planes
+// lay: the layout of y6, planes or h2 (unscaled)
 hipError_t launch_silu_act(const float* x, float* yf, unsigned short* y6, long long rows, int C, hipStream_t s,
-                           int h2 = 0);
+                           Layout lay = LAYOUT_PLANES);
 hipError_t launch_spec_mag(const float* spec, float* mag, unsigned short* mag6, float* loglin, long long rows, int nbins,
                            int ld_out, hipStream_t s);
-hipError_t launch_split_planes(const float* x, unsigned short* y6, long long rows, int C, int compact, hipStream_t s);
+hipError_t launch_split_planes(const float* x, unsigned short* y6, long long rows, int C, Layout lay, hipStream_t s);
 // clip_len (may be null; device): the rows are clips of `frames` rows, and a row at or beyond its
 // clip's length is written as zeros without reading (or counting) its index
 hipError_t launch_gather_rows(const float* table, int ntable, const int32_t* idx, long long rows, int width,

@@ -27,7 +27,7 @@ __device__ __forceinline__ float wave_sum(float v) {
 template <int NV>
 __device__ __forceinline__ void ln_finish(f32x4 (&v)[NV], int C, float eps, int cf, const float* __restrict__ w,
                                           const float* __restrict__ b, float* __restrict__ yrow,
-                                          unsigned short* __restrict__ y6, int y6c, long long row, int lane,
+                                          unsigned short* __restrict__ y6, Layout lay, long long row, int lane,
                                           int* __restrict__ ash_row, float* __restrict__ amax_row) {
   float s = 0.f;
 #pragma unroll
@@ -69,7 +69,7 @@ __device__ __forceinline__ void ln_finish(f32x4 (&v)[NV], int C, float eps, int 
   // h2 (an h3 one-tap consumer): the row scaled by 2^h2_shift(its exact max |o|), the shift and the
   // max recorded per row (dcx_kernels.h)
   float sc = 1.0f;
-  if (y6c == 3) {
+  if (lay == LAYOUT_H2) {
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) am = fmaxf(am, __shfl_xor(am, off, 64));
     const int sh = h2_shift(am);
@@ -83,8 +83,8 @@ __device__ __forceinline__ void ln_finish(f32x4 (&v)[NV], int C, float eps, int 
   for (int i = 0; i < NV; ++i) {
     const int c = (lane + 64 * i) * 4;
     const f32x4 o = ov[i];
-    if (y6c == 1) store_bf16x4(y6, row, C, c, o.x, o.y, o.z, o.w);
-    else if (y6c == 3) store_h2_4(y6, row, C, c, o.x, o.y, o.z, o.w, sc);
+    if (lay == LAYOUT_BF16) store_bf16x4(y6, row, C, c, o.x, o.y, o.z, o.w);
+    else if (lay == LAYOUT_H2) store_h2_4(y6, row, C, c, o.x, o.y, o.z, o.w, sc);
     else store_planes4(y6, row, C, c, o.x, o.y, o.z, o.w);
   }
 }

@@ -12,7 +12,7 @@ namespace dcx {
 
 template <int NV>
 __global__ void __launch_bounds__(256) ln_rows_kernel(const float* __restrict__ x, float* __restrict__ y,
-                                                       unsigned short* __restrict__ y6, int y6c, const float* __restrict__ w,
+                                                       unsigned short* __restrict__ y6, Layout lay, const float* __restrict__ w,
                                                        const float* __restrict__ b, long long rows, float eps, int cf,
                                                        int* ash_row, float* amax_row) {
   const int lane = threadIdx.x & 63;
@@ -22,18 +22,18 @@ __global__ void __launch_bounds__(256) ln_rows_kernel(const float* __restrict__ 
   f32x4 v[NV];
 #pragma unroll
   for (int i = 0; i < NV; ++i) v[i] = *reinterpret_cast<const f32x4*>(x + row * C + (lane + 64 * i) * 4);
-  ln_finish<NV>(v, C, eps, cf, w, b, y ? y + row * C : nullptr, y6, y6c, row, lane, ash_row, amax_row);
+  ln_finish<NV>(v, C, eps, cf, w, b, y ? y + row * C : nullptr, y6, lay, row, lane, ash_row, amax_row);
 }
 
-hipError_t launch_ln_rows(const float* x, float* y, unsigned short* y6, int y6c, const float* w, const float* b,
+hipError_t launch_ln_rows(const float* x, float* y, unsigned short* y6, Layout lay, const float* w, const float* b,
                           long long rows, int C, float eps, int cf, hipStream_t s, int* ash_row, float* amax_row) {
-  if (y6 && y6c == 3 && !ash_row) return hipErrorInvalidValue;
+  if (y6 && lay == LAYOUT_H2 && !ash_row) return hipErrorInvalidValue;
   dim3 grid((unsigned)((rows + 3) / 4)), block(256);
   switch (C) {
-    case 256: hipLaunchKernelGGL(ln_rows_kernel<1>, grid, block, 0, s, x, y, y6, y6c, w, b, rows, eps, cf, ash_row, amax_row); break;
-    case 512: hipLaunchKernelGGL(ln_rows_kernel<2>, grid, block, 0, s, x, y, y6, y6c, w, b, rows, eps, cf, ash_row, amax_row); break;
-    case 768: hipLaunchKernelGGL(ln_rows_kernel<3>, grid, block, 0, s, x, y, y6, y6c, w, b, rows, eps, cf, ash_row, amax_row); break;
-    case 1024: hipLaunchKernelGGL(ln_rows_kernel<4>, grid, block, 0, s, x, y, y6, y6c, w, b, rows, eps, cf, ash_row, amax_row); break;
+    case 256: hipLaunchKernelGGL(ln_rows_kernel<1>, grid, block, 0, s, x, y, y6, lay, w, b, rows, eps, cf, ash_row, amax_row); break;
+    case 512: hipLaunchKernelGGL(ln_rows_kernel<2>, grid, block, 0, s, x, y, y6, lay, w, b, rows, eps, cf, ash_row, amax_row); break;
+    case 768: hipLaunchKernelGGL(ln_rows_kernel<3>, grid, block, 0, s, x, y, y6, lay, w, b, rows, eps, cf, ash_row, amax_row); break;
+    case 1024: hipLaunchKernelGGL(ln_rows_kernel<4>, grid, block, 0, s, x, y, y6, lay, w, b, rows, eps, cf, ash_row, amax_row); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -49,7 +49,7 @@ hipError_t launch_ln_rows(const float* x, float* y, unsigned short* y6, int y6c,
 // DW_R = 16 rows per workgroup; 4 when 16-row tiles would leave most CUs idle (a streaming hop).
 template <int NV, int DW_R>
 __global__ void __launch_bounds__(256) dwconv_ln_kernel(const float* __restrict__ x, float* __restrict__ y,
-                                                         unsigned short* __restrict__ y6, int y6c,
+                                                         unsigned short* __restrict__ y6, Layout lay,
                                                          const float* __restrict__ dww, const float* __restrict__ dwb,
                                                          const float* __restrict__ lnw, const float* __restrict__ lnb,
                                                          int L, int tiles, int bf, int* ash_row, float* amax_row) {
@@ -106,7 +106,7 @@ __global__ void __launch_bounds__(256) dwconv_ln_kernel(const float* __restrict_
       if (bf) v[i] = round_bf16x4(v[i]);
     }
     const long long row = (long long)bidx * L + t;
-    ln_finish<NV>(v, C, 1e-6f, 0, lnw, lnb, y ? y + row * C : nullptr, y6, y6c, row, lane, ash_row, amax_row);
+    ln_finish<NV>(v, C, 1e-6f, 0, lnw, lnb, y ? y + row * C : nullptr, y6, lay, row, lane, ash_row, amax_row);
   }
 }
 
@@ -120,7 +120,7 @@ __global__ void __launch_bounds__(256) dwconv_ln_kernel(const float* __restrict_
 // (slot = row mod S).
 template <int NV, int RW, int D>
 __global__ void __launch_bounds__(256) dwconv_ln_run_kernel(const float* __restrict__ x, float* __restrict__ y,
-                                                             unsigned short* __restrict__ y6, int y6c,
+                                                             unsigned short* __restrict__ y6, Layout lay,
                                                              const float* __restrict__ dww, const float* __restrict__ dwb,
                                                              const float* __restrict__ lnw, const float* __restrict__ lnb,
                                                              int L, int runs, long long nruns, int bf, int* ash_row,
@@ -183,13 +183,13 @@ __global__ void __launch_bounds__(256) dwconv_ln_run_kernel(const float* __restr
         if (bf) v[i] = round_bf16x4(v[i]);
       }
       const long long row = (long long)bidx * L + tk;
-      ln_finish<NV>(v, C, 1e-6f, 0, lnw, lnb, y ? y + row * C : nullptr, y6, y6c, row, lane, ash_row, amax_row);
+      ln_finish<NV>(v, C, 1e-6f, 0, lnw, lnb, y ? y + row * C : nullptr, y6, lay, row, lane, ash_row, amax_row);
     }
   }
 }
 
 template <int NV>
-static void launch_dwconv_ln_nv(const float* x, float* y, unsigned short* y6, int y6c, const float* dww,
+static void launch_dwconv_ln_nv(const float* x, float* y, unsigned short* y6, Layout lay, const float* dww,
                                 const float* dwb, const float* lnw, const float* lnb, int batch, int L, int rw, int bf,
                                 hipStream_t s, int* ash_row, float* amax_row) {
   const int runs = (L + rw - 1) / rw;
@@ -197,17 +197,17 @@ static void launch_dwconv_ln_nv(const float* x, float* y, unsigned short* y6, in
   const dim3 grid((unsigned)((nruns + 3) / 4)), block(256);
   constexpr int D = NV >= 4 ? 1 : 2;  // rows prefetched beyond the window (registers: 2 waves per SIMD at C = 1024)
   switch (rw) {
-    case 32: hipLaunchKernelGGL((dwconv_ln_run_kernel<NV, 32, D>), grid, block, 0, s, x, y, y6, y6c, dww, dwb, lnw, lnb, L, runs, nruns, bf, ash_row, amax_row); break;
-    case 16: hipLaunchKernelGGL((dwconv_ln_run_kernel<NV, 16, D>), grid, block, 0, s, x, y, y6, y6c, dww, dwb, lnw, lnb, L, runs, nruns, bf, ash_row, amax_row); break;
-    case 8: hipLaunchKernelGGL((dwconv_ln_run_kernel<NV, 8, D>), grid, block, 0, s, x, y, y6, y6c, dww, dwb, lnw, lnb, L, runs, nruns, bf, ash_row, amax_row); break;
-    default: hipLaunchKernelGGL((dwconv_ln_run_kernel<NV, 4, D>), grid, block, 0, s, x, y, y6, y6c, dww, dwb, lnw, lnb, L, runs, nruns, bf, ash_row, amax_row); break;
+    case 32: hipLaunchKernelGGL((dwconv_ln_run_kernel<NV, 32, D>), grid, block, 0, s, x, y, y6, lay, dww, dwb, lnw, lnb, L, runs, nruns, bf, ash_row, amax_row); break;
+    case 16: hipLaunchKernelGGL((dwconv_ln_run_kernel<NV, 16, D>), grid, block, 0, s, x, y, y6, lay, dww, dwb, lnw, lnb, L, runs, nruns, bf, ash_row, amax_row); break;
+    case 8: hipLaunchKernelGGL((dwconv_ln_run_kernel<NV, 8, D>), grid, block, 0, s, x, y, y6, lay, dww, dwb, lnw, lnb, L, runs, nruns, bf, ash_row, amax_row); break;
+    default: hipLaunchKernelGGL((dwconv_ln_run_kernel<NV, 4, D>), grid, block, 0, s, x, y, y6, lay, dww, dwb, lnw, lnb, L, runs, nruns, bf, ash_row, amax_row); break;
   }
 }
 
-hipError_t launch_dwconv_ln(const float* x, float* y, unsigned short* y6, int y6c, const float* dww, const float* dwb,
+hipError_t launch_dwconv_ln(const float* x, float* y, unsigned short* y6, Layout lay, const float* dww, const float* dwb,
                             const float* lnw, const float* lnb, int batch, int L, int C, int bf16, const Knobs* kn,
                             hipStream_t s, int* ash_row, float* amax_row) {
-  if (y6 && y6c == 3 && !ash_row) return hipErrorInvalidValue;
+  if (y6 && lay == LAYOUT_H2 && !ash_row) return hipErrorInvalidValue;
   const bool tiled = kn && kn->dwconv_tiled;  // A/B and tests: the round-2 tiled kernel (same bits)
   const long long rows = (long long)batch * L;
   // below 8192 rows (a streaming hop: 93 rows) the tiled kernel's 4-row tiles, one row per wave,
@@ -217,10 +217,10 @@ hipError_t launch_dwconv_ln(const float* x, float* y, unsigned short* y6, int y6
     const int rw = rows >= 2048LL * 32 ? 32 : rows >= 2048LL * 16 ? 16 : rows >= 2048LL * 8 ? 8 : 4;
     if ((long long)batch * ((L + rw - 1) / rw) / 4 >= (1LL << 31)) return hipErrorInvalidValue;
     switch (C) {
-      case 256: launch_dwconv_ln_nv<1>(x, y, y6, y6c, dww, dwb, lnw, lnb, batch, L, rw, bf16, s, ash_row, amax_row); break;
-      case 512: launch_dwconv_ln_nv<2>(x, y, y6, y6c, dww, dwb, lnw, lnb, batch, L, rw, bf16, s, ash_row, amax_row); break;
-      case 768: launch_dwconv_ln_nv<3>(x, y, y6, y6c, dww, dwb, lnw, lnb, batch, L, rw, bf16, s, ash_row, amax_row); break;
-      case 1024: launch_dwconv_ln_nv<4>(x, y, y6, y6c, dww, dwb, lnw, lnb, batch, L, rw, bf16, s, ash_row, amax_row); break;
+      case 256: launch_dwconv_ln_nv<1>(x, y, y6, lay, dww, dwb, lnw, lnb, batch, L, rw, bf16, s, ash_row, amax_row); break;
+      case 512: launch_dwconv_ln_nv<2>(x, y, y6, lay, dww, dwb, lnw, lnb, batch, L, rw, bf16, s, ash_row, amax_row); break;
+      case 768: launch_dwconv_ln_nv<3>(x, y, y6, lay, dww, dwb, lnw, lnb, batch, L, rw, bf16, s, ash_row, amax_row); break;
+      case 1024: launch_dwconv_ln_nv<4>(x, y, y6, lay, dww, dwb, lnw, lnb, batch, L, rw, bf16, s, ash_row, amax_row); break;
       default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -231,14 +231,14 @@ hipError_t launch_dwconv_ln(const float* x, float* y, unsigned short* y6, int y6
   if ((long long)batch * tiles >= (1LL << 31)) return hipErrorInvalidValue;
   dim3 grid((unsigned)(batch * tiles)), block(256);
   switch (C) {
-    case 256: if (small) hipLaunchKernelGGL((dwconv_ln_kernel<1, 4>), grid, block, 0, s, x, y, y6, y6c, dww, dwb, lnw, lnb, L, tiles, bf16, ash_row, amax_row);
-      else hipLaunchKernelGGL((dwconv_ln_kernel<1, 16>), grid, block, 0, s, x, y, y6, y6c, dww, dwb, lnw, lnb, L, tiles, bf16, ash_row, amax_row); break;
-    case 512: if (small) hipLaunchKernelGGL((dwconv_ln_kernel<2, 4>), grid, block, 0, s, x, y, y6, y6c, dww, dwb, lnw, lnb, L, tiles, bf16, ash_row, amax_row);
-      else hipLaunchKernelGGL((dwconv_ln_kernel<2, 16>), grid, block, 0, s, x, y, y6, y6c, dww, dwb, lnw, lnb, L, tiles, bf16, ash_row, amax_row); break;
-    case 768: if (small) hipLaunchKernelGGL((dwconv_ln_kernel<3, 4>), grid, block, 0, s, x, y, y6, y6c, dww, dwb, lnw, lnb, L, tiles, bf16, ash_row, amax_row);
-      else hipLaunchKernelGGL((dwconv_ln_kernel<3, 16>), grid, block, 0, s, x, y, y6, y6c, dww, dwb, lnw, lnb, L, tiles, bf16, ash_row, amax_row); break;
-    case 1024: if (small) hipLaunchKernelGGL((dwconv_ln_kernel<4, 4>), grid, block, 0, s, x, y, y6, y6c, dww, dwb, lnw, lnb, L, tiles, bf16, ash_row, amax_row);
-      else hipLaunchKernelGGL((dwconv_ln_kernel<4, 16>), grid, block, 0, s, x, y, y6, y6c, dww, dwb, lnw, lnb, L, tiles, bf16, ash_row, amax_row); break;
+    case 256: if (small) hipLaunchKernelGGL((dwconv_ln_kernel<1, 4>), grid, block, 0, s, x, y, y6, lay, dww, dwb, lnw, lnb, L, tiles, bf16, ash_row, amax_row);
+      else hipLaunchKernelGGL((dwconv_ln_kernel<1, 16>), grid, block, 0, s, x, y, y6, lay, dww, dwb, lnw, lnb, L, tiles, bf16, ash_row, amax_row); break;
+    case 512: if (small) hipLaunchKernelGGL((dwconv_ln_kernel<2, 4>), grid, block, 0, s, x, y, y6, lay, dww, dwb, lnw, lnb, L, tiles, bf16, ash_row, amax_row);
+      else hipLaunchKernelGGL((dwconv_ln_kernel<2, 16>), grid, block, 0, s, x, y, y6, lay, dww, dwb, lnw, lnb, L, tiles, bf16, ash_row, amax_row); break;
+    case 768: if (small) hipLaunchKernelGGL((dwconv_ln_kernel<3, 4>), grid, block, 0, s, x, y, y6, lay, dww, dwb, lnw, lnb, L, tiles, bf16, ash_row, amax_row);
+      else hipLaunchKernelGGL((dwconv_ln_kernel<3, 16>), grid, block, 0, s, x, y, y6, lay, dww, dwb, lnw, lnb, L, tiles, bf16, ash_row, amax_row); break;
+    case 1024: if (small) hipLaunchKernelGGL((dwconv_ln_kernel<4, 4>), grid, block, 0, s, x, y, y6, lay, dww, dwb, lnw, lnb, L, tiles, bf16, ash_row, amax_row);
+      else hipLaunchKernelGGL((dwconv_ln_kernel<4, 16>), grid, block, 0, s, x, y, y6, lay, dww, dwb, lnw, lnb, L, tiles, bf16, ash_row, amax_row); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -331,8 +331,9 @@ __global__ void __launch_bounds__(256) silu_act_kernel(const float* __restrict__
   }
 }
 
-hipError_t launch_silu_act(const float* x, float* yf, unsigned short* y6, long long rows, int C, hipStream_t s, int h2) {
-  if (C % 8 || rows < 0 || (h2 && y6)) return hipErrorInvalidValue;
+hipError_t launch_silu_act(const float* x, float* yf, unsigned short* y6, long long rows, int C, hipStream_t s,
+                           Layout lay) {
+  if (C % 8 || rows < 0 || (y6 && lay != LAYOUT_PLANES)) return hipErrorInvalidValue;  // h2: launch_h2_ranged
   const long long total4 = rows * C / 4;
   if (total4 == 0) return hipSuccess;
   const long long nb = (total4 + 255) / 256;
@@ -487,23 +488,23 @@ hipError_t launch_h2_ranged(const float* x, float* yf, unsigned short* y6, int b
 // fp32 [rows][C] -> planes, or (compact) bf16 [rows][C] (boundary conversion for tensors handed in
 // by the caller; the h2 layout goes through launch_h2_ranged).
 __global__ void __launch_bounds__(256) split_planes_kernel(const float* __restrict__ x, unsigned short* __restrict__ y6,
-                                                            long long rows, int C, int compact) {
+                                                            long long rows, int C, Layout lay) {
   const long long total4 = rows * C / 4;
   for (long long i4 = (long long)blockIdx.x * blockDim.x + threadIdx.x; i4 < total4;
        i4 += (long long)gridDim.x * blockDim.x) {
     const f32x4 v = *reinterpret_cast<const f32x4*>(x + i4 * 4);
     const long long i = i4 * 4;
-    if (compact == 1) store_bf16x4(y6, i / C, C, (int)(i % C), v.x, v.y, v.z, v.w);
+    if (lay == LAYOUT_BF16) store_bf16x4(y6, i / C, C, (int)(i % C), v.x, v.y, v.z, v.w);
     else store_planes4(y6, i / C, C, (int)(i % C), v.x, v.y, v.z, v.w);
   }
 }
 
-hipError_t launch_split_planes(const float* x, unsigned short* y6, long long rows, int C, int compact, hipStream_t s) {
-  if (C % 8 || compact < 0 || compact > 1) return hipErrorInvalidValue;
+hipError_t launch_split_planes(const float* x, unsigned short* y6, long long rows, int C, Layout lay, hipStream_t s) {
+  if (C % 8 || (lay != LAYOUT_PLANES && lay != LAYOUT_BF16)) return hipErrorInvalidValue;  // planes or compact only
   const long long total4 = rows * C / 4;
   unsigned g = (unsigned)((total4 + 255) / 256);
   if (g > 8192) g = 8192;
-  hipLaunchKernelGGL(split_planes_kernel, dim3(g), dim3(256), 0, s, x, y6, rows, C, compact);
+  hipLaunchKernelGGL(split_planes_kernel, dim3(g), dim3(256), 0, s, x, y6, rows, C, lay);
   return hipGetLastError();
 }
 

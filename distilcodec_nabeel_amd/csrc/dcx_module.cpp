@@ -58,14 +58,14 @@ static int resblock_input(dcx_codec* h, const float* x, Act& xs, bool silu_on_lo
   float* amax = ra.amax();
   xs.r = Rng{};
   xs.r.amax = amax;
-  if (!silu_on_load && xs.h2) {
+  if (!silu_on_load && xs.lay == LAYOUT_H2) {
     int* sh = ra.ash();
     LAUNCH(h, s, "h2_ranged", 0, 12.0 * M * C,
            dcx::launch_h2_ranged(x, nullptr, xs.p, B, L, C, 1, 0.f, amax, sh, h->rflag, s));
     xs.r.ash = sh;
   } else {
     LAUNCH(h, s, "clip_amax", 0, 4.0 * M * C, dcx::launch_clip_amax(x, B, L, C, amax, s));
-    if (!silu_on_load) LAUNCH(h, s, "silu_act", 0, 10.0 * M * C, dcx::launch_silu_act(x, xs.f, xs.p, M, C, s, 0));
+    if (!silu_on_load) LAUNCH(h, s, "silu_act", 0, 10.0 * M * C, dcx::launch_silu_act(x, xs.f, xs.p, M, C, s));
   }
   return DCX_OK;
 }
@@ -94,9 +94,8 @@ int stage_module(dcx_codec* h, const std::string& m, const float* x, int B, int 
     Act ln = conv_input(h, ws, (size_t)M * c.enc_dims[a - 1]);
     if (x6_mode(h)) ln.row_ash = ws.i((size_t)M);
     WS_READY(h, ws, "workspace too small for the module");
-    ln.c1 = ln.p && takes_compact(h, h->ds_conv[a], M);
-    ln.h2 = ln.p && ln.row_ash && takes_h3(h, h->ds_conv[a]);
-    ln.r.ash_row = ln.h2 ? ln.row_ash : nullptr;
+    ln.lay = input_layout(h, h->ds_conv[a], M, ln.row_ash);
+    ln.r.ash_row = ln.lay == LAYOUT_H2 ? ln.row_ash : nullptr;
     RUN(run_ln(h, h->ds_ln[a], x, ln, M, s));
     ConvCall cd = pointwise(ln, M);
     cd.y = y;
@@ -108,7 +107,7 @@ int stage_module(dcx_codec* h, const std::string& m, const float* x, int B, int 
     const int D = c.vq_dim;
     CAct in(x, nullptr);
     // the down conv in h3 as in the pipeline (range floor: the encoder's final LayerNorm bound)
-    RUN(ensure_planes(h, in, M, D, ws, s, false, down && takes_h3(h, h->vq_down), 0));
+    RUN(ensure_planes(h, in, M, D, ws, s, h2_if(down && takes_h3(h, h->vq_down)), 0));
     Act ln = conv_input(h, ws, (size_t)M * D);
     Act hid = conv_input(h, ws, (size_t)M * 4 * D);
     row_ranges(h, ws, M, ln, hid);
@@ -120,7 +119,7 @@ int stage_module(dcx_codec* h, const std::string& m, const float* x, int B, int 
   }
   if (m == "quantizer.grvq.rvqs.0.project_in") {  // residual_vq.py:152
     CAct in(x, nullptr);
-    RUN(ensure_planes(h, in, M, c.vq_dim, ws, s, false, takes_h3(h, h->vq_pin), 0));
+    RUN(ensure_planes(h, in, M, c.vq_dim, ws, s, h2_if(takes_h3(h, h->vq_pin)), 0));
     WS_READY(h, ws, "workspace too small for the module");
     ConvCall cp = pointwise(in, M);
     cp.y = y;
@@ -159,7 +158,7 @@ int stage_module(dcx_codec* h, const std::string& m, const float* x, int B, int 
     // (vector_quantize_pytorch.py:462-498), x being project_in's bf16 output; row_sqnorm's |x - bf16(x)|^2
     // keeps the prefilter's bound valid for an input that is not bf16-valued.
     const bool x6 = x6_mode(h);
-    const int xl = vq_xlayout(h);
+    const Layout xl = vq_xlayout(h);
     const int ntiles = x6 ? dcx::vq_prefilter_ntiles(NC, CD, xl) : dcx::vq_argmin_ntiles(NC);
     unsigned short* P6 = x6 ? ws.u16((size_t)M * CD * 3) : nullptr;
     const VqScratch vs = vq_scratch(h, ws, M, ntiles, x6);
@@ -170,7 +169,7 @@ int stage_module(dcx_codec* h, const std::string& m, const float* x, int B, int 
   if (!h->has_gen && m.rfind("generator.", 0) == 0) return fail(h, DCX_ERR_STATE, "generator weights were not finalized");
   if (m == "generator.conv_pre") {  // generators.py:121
     CAct in(x, nullptr);
-    RUN(ensure_planes(h, in, M, c.vq_dim, ws, s, false, takes_h3_conv(h, h->conv_pre, L), B));
+    RUN(ensure_planes(h, in, M, c.vq_dim, ws, s, h2_if(takes_h3_conv(h, h->conv_pre, L)), B));
     WS_READY(h, ws, "workspace too small for the module");
     ConvCall cc = framed(in, B, L, c.vq_dim);
     cc.y = y;
@@ -188,7 +187,7 @@ int stage_module(dcx_codec* h, const std::string& m, const float* x, int B, int 
   if (match_idx(m, "generator.ups.%d%n", &a) && a >= 0 && a < c.n_ups) {
     const ConvW& up = h->ups[a];
     CAct in(x, nullptr);
-    if (!(x6_mode(h) && f32_input_ok(up))) RUN(ensure_planes(h, in, M, up.cin, ws, s, false, takes_h3_conv(h, up, L), B));
+    if (!(x6_mode(h) && f32_input_ok(up))) RUN(ensure_planes(h, in, M, up.cin, ws, s, h2_if(takes_h3_conv(h, up, L)), B));
     WS_READY(h, ws, "workspace too small for the module");
     ConvCall cc = framed(in, B, L, up.cin);
     cc.y = y;
@@ -207,7 +206,7 @@ int stage_module(dcx_codec* h, const std::string& m, const float* x, int B, int 
     HIPCHK(h, dcx::launch_zero_words(ra.base, (long long)RangeArena::kSlots * B, s));
     const bool silu_on_load = x6_mode(h) && f32_input_ok(w0);
     Act XSi = in_form(XS, w0), Tbi = in_form(Tb, w0);
-    XSi.h2 = Tbi.h2 = h3_stage(h, a, L);
+    XSi.lay = Tbi.lay = h2_if(h3_stage(h, a, L));
     HIPCHK(h, hipMemcpyAsync(y, x, sizeof(float) * M * C, hipMemcpyDeviceToDevice, s));
     RUN(resblock_input(h, y, XSi, silu_on_load, B, L, C, ra, s));
     Rng st = XSi.r;  // the state's range: its measured max |.| (and, in h2, its silu's shift)
@@ -221,7 +220,7 @@ int stage_module(dcx_codec* h, const std::string& m, const float* x, int B, int 
       c1.silu_to(Tbi);
       c1.yb = prog_conv(w1, st);
       c1.y_amax = ra.amax();
-      c1.y_ash = Tbi.h2 ? ra.ash() : nullptr;
+      c1.y_ash = Tbi.lay == LAYOUT_H2 ? ra.ash() : nullptr;
       RUN(run_conv(h, w1, c1, s));
       const Rng tr{c1.y_ash, 0, c1.y_amax, 0.f};
       Act tin = Tbi;
@@ -235,7 +234,7 @@ int stage_module(dcx_codec* h, const std::string& m, const float* x, int B, int 
       prog_add(c2.yb, 1.0f, Rng{nullptr, 0, st.amax, 0.f});
       prog_add(c2.yb, w2.g_abs, tr);
       c2.y_amax = ra.amax();
-      c2.y_ash = !silu_on_load && ci < 2 && XSi.h2 ? ra.ash() : nullptr;
+      c2.y_ash = !silu_on_load && ci < 2 && XSi.lay == LAYOUT_H2 ? ra.ash() : nullptr;
       RUN(run_conv(h, w2, c2, s));
       st = Rng{c2.y_ash, 0, c2.y_amax, 0.f};
     }
@@ -263,13 +262,13 @@ int stage_module(dcx_codec* h, const std::string& m, const float* x, int B, int 
     const bool silu_on_load = x6_mode(h) && f32_input_ok(w0);
     HIPCHK(h, hipMemcpyAsync(X, x, sizeof(float) * per, hipMemcpyDeviceToDevice, s));
     pb.X = X;
-    const bool h3 = h3_stage(h, a, L);
+    const Layout lay = h2_if(h3_stage(h, a, L));
     pb.XS = in_form(XS, w0);
-    pb.XS.h2 = h3;
+    pb.XS.lay = lay;
     for (int rb = 0; rb < c.n_res; ++rb) {
       pb.RS[rb] = in_form(RS[rb], w0);
       pb.Tb_in[rb] = in_form(pb.Tb[rb], w0);
-      pb.RS[rb].h2 = pb.Tb_in[rb].h2 = h3;
+      pb.RS[rb].lay = pb.Tb_in[rb].lay = lay;
     }
     RUN(resblock_input(h, X, pb.XS, silu_on_load, B, L, C, ra, s));
     pb.Mx = y;

@@ -76,7 +76,7 @@ __device__ __forceinline__ void store_bf16x4(unsigned short* base, long long row
   *reinterpret_cast<s16x4p*>(base + row * (long long)C + c) = hv;
 }
 
-// "hm" layout (y_compact == 2; no kernel reads it any more and the host rejects it, only the
+// "hm" layout (layout value 2, no enumerator; no kernel reads it any more and the host rejects it, only the
 // unreachable arms of the conv epilogues still name these stores): the hi and mid planes per 32
 // channels as [rows][C/32][8 pieces][8] bf16, piece = ((c >> 3) & 3) * 2 + plane (4 B per element).
 // Store 4 consecutive channels c..c+3 (c % 4 == 0).

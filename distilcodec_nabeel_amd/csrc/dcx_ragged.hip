@@ -111,7 +111,7 @@ hipError_t launch_ragged_unfold(const void* x, void* y, const RaggedSeg& g, int 
 // ---------------------------------------------------------------------------------------------
 template <int NV, int DW_R>
 __global__ void __launch_bounds__(256) dwconv_ln_seg_kernel(const float* __restrict__ x, float* __restrict__ y,
-                                                             unsigned short* __restrict__ y6, int y6c,
+                                                             unsigned short* __restrict__ y6, Layout lay,
                                                              const float* __restrict__ dww, const float* __restrict__ dwb,
                                                              const float* __restrict__ lnw, const float* __restrict__ lnb,
                                                              const RaggedSeg g, const int* __restrict__ cu_tiles, int bf,
@@ -172,7 +172,7 @@ __global__ void __launch_bounds__(256) dwconv_ln_seg_kernel(const float* __restr
       if (bf) v[i] = round_bf16x4(v[i]);
     }
     const long long row = base + t;
-    ln_finish<NV>(v, C, 1e-6f, 0, lnw, lnb, y ? y + row * C : nullptr, y6, y6c, row, lane, ash_row, amax_row);
+    ln_finish<NV>(v, C, 1e-6f, 0, lnw, lnb, y ? y + row * C : nullptr, y6, lay, row, lane, ash_row, amax_row);
   }
 }
 
@@ -182,7 +182,7 @@ __global__ void __launch_bounds__(256) dwconv_ln_seg_kernel(const float* __restr
 // ---------------------------------------------------------------------------------------------
 template <int NV, int RW, int D>
 __global__ void __launch_bounds__(256) dwconv_ln_run_seg_kernel(const float* __restrict__ x, float* __restrict__ y,
-                                                                 unsigned short* __restrict__ y6, int y6c,
+                                                                 unsigned short* __restrict__ y6, Layout lay,
                                                                  const float* __restrict__ dww,
                                                                  const float* __restrict__ dwb,
                                                                  const float* __restrict__ lnw,
@@ -247,15 +247,15 @@ __global__ void __launch_bounds__(256) dwconv_ln_run_seg_kernel(const float* __r
         if (bf) v[i] = round_bf16x4(v[i]);
       }
       const long long row = base + tk;
-      ln_finish<NV>(v, C, 1e-6f, 0, lnw, lnb, y ? y + row * C : nullptr, y6, y6c, row, lane, ash_row, amax_row);
+      ln_finish<NV>(v, C, 1e-6f, 0, lnw, lnb, y ? y + row * C : nullptr, y6, lay, row, lane, ash_row, amax_row);
     }
   }
 }
 
-#define DCX_RAGGED_ARGS x, y, y6, y6c, dww, dwb, lnw, lnb, g
+#define DCX_RAGGED_ARGS x, y, y6, lay, dww, dwb, lnw, lnb, g
 
 template <int NV>
-static void launch_run_seg_nv(const float* x, float* y, unsigned short* y6, int y6c, const float* dww, const float* dwb,
+static void launch_run_seg_nv(const float* x, float* y, unsigned short* y6, Layout lay, const float* dww, const float* dwb,
                               const float* lnw, const float* lnb, const RaggedSeg& g, int bf, hipStream_t s,
                               int* ash_row, float* amax_row) {
   const dim3 grid((unsigned)((g.n_run + 3) / 4)), block(256);
@@ -269,7 +269,7 @@ static void launch_run_seg_nv(const float* x, float* y, unsigned short* y6, int 
 }
 
 template <int NV>
-static void launch_tiled_seg_nv(const float* x, float* y, unsigned short* y6, int y6c, const float* dww,
+static void launch_tiled_seg_nv(const float* x, float* y, unsigned short* y6, Layout lay, const float* dww,
                                 const float* dwb, const float* lnw, const float* lnb, const RaggedSeg& g, bool small,
                                 int bf, hipStream_t s, int* ash_row, float* amax_row) {
   const dim3 block(256);
@@ -279,10 +279,10 @@ static void launch_tiled_seg_nv(const float* x, float* y, unsigned short* y6, in
     hipLaunchKernelGGL((dwconv_ln_seg_kernel<NV, 16>), dim3((unsigned)g.n_t16), block, 0, s, DCX_RAGGED_ARGS, g.cu_t16, bf, ash_row, amax_row);
 }
 
-hipError_t launch_dwconv_ln_ragged(const float* x, float* y, unsigned short* y6, int y6c, const float* dww,
+hipError_t launch_dwconv_ln_ragged(const float* x, float* y, unsigned short* y6, Layout lay, const float* dww,
                                    const float* dwb, const float* lnw, const float* lnb, const RaggedSeg& g, int C,
                                    int bf16, const Knobs* kn, hipStream_t s, int* ash_row, float* amax_row) {
-  if (y6 && y6c == 3 && !ash_row) return hipErrorInvalidValue;
+  if (y6 && lay == LAYOUT_H2 && !ash_row) return hipErrorInvalidValue;
   if (g.batch < 1 || g.rows < 1 || g.n_t16 < 1 || g.n_t4 < 1 || g.n_run < 1) return hipErrorInvalidValue;
   const bool tiled = kn && kn->dwconv_tiled;
   // launch_dwconv_ln's thresholds: the register-ring runs from 8192 rows on, 4-row tiles while 16-row

@@ -90,8 +90,8 @@ static int fork_join(dcx_codec* h, hipStream_t s, F0 first, F1 second) {
   return DCX_OK;
 }
 
-// Rows [r0, ...) (clips b0 on) of a [B][T][C] activation in its layout (planes 3, h2 2, compact 1
-// ushorts per element), with its per-row and per-clip range pointers.
+// Rows [r0, ...) (clips b0 on) of a [B][T][C] activation in its layout, with its per-row and per-clip
+// range pointers.
 // The three a.r offsets are unreached today, so no test exercises them: the activations that are split
 // carry no consumer-side ranges (mel has none, feat's consumer reads the whole batch's table through
 // the unsplit Act, z carries none).  The live offsets of a split are the producer-side row_ash /
@@ -99,7 +99,7 @@ static int fork_join(dcx_codec* h, hipStream_t s, F0 first, F1 second) {
 template <class A>
 static A act_rows(A a, int b0, long long r0, long long C) {
   if (a.f) a.f += r0 * C;
-  if (a.p) a.p += r0 * C * (a.c1 ? 1 : a.h2 ? 2 : 3);
+  if (a.p) a.p += r0 * C * layout_u16(a.lay);
   if (a.r.ash) a.r.ash += b0;
   if (a.r.amax) a.r.amax += b0;
   if (a.r.ash_row) a.r.ash_row += r0;
@@ -130,7 +130,7 @@ static int encode_clips(dcx_codec* h, const CAct& mel, int B, int T, Act feat, f
   const dcx_config& c = h->cfg;
   const long long M = (long long)B * T;
   if (rg) {
-    if (!mel.p || !hid.p || mel.c1 || mel.h2) return fail(h, DCX_ERR_STATE, "internal: ragged stem needs planes");
+    if (!mel.p || !hid.p || mel.lay != LAYOUT_PLANES) return fail(h, DCX_ERR_STATE, "internal: ragged stem needs planes");
     LAUNCH(h, s, "ragged_unfold", 0, 6.0 * M * c.n_mels * (1 + h->stem.taps),
            dcx::launch_ragged_unfold(mel.p, hid.p, *rg, c.n_mels * 6, h->stem.taps, s));
     ConvCall cc = pointwise(CAct(nullptr, hid.p), M);
@@ -145,16 +145,15 @@ static int encode_clips(dcx_codec* h, const CAct& mel, int B, int T, Act feat, f
   RUN(run_ln(h, h->stem_ln, xa, Act{xb, nullptr}, M, s, /*bf16_in=*/true));
   for (int i = 0; i < 4; ++i) {
     if (i > 0) {
-      ln.c1 = ln.p && takes_compact(h, h->ds_conv[i], M);
-      ln.h2 = ln.p && ln.row_ash && takes_h3(h, h->ds_conv[i]);  // the downsample 1x1 conv on conv_gemm_x3dw
+      ln.lay = input_layout(h, h->ds_conv[i], M, ln.row_ash);  // h2: the downsample 1x1 conv on conv_gemm_x3dw
       ln.r = Rng{};
-      ln.r.ash_row = ln.h2 ? ln.row_ash : nullptr;  // row-scaled by run_ln
+      ln.r.ash_row = ln.lay == LAYOUT_H2 ? ln.row_ash : nullptr;  // row-scaled by run_ln
       RUN(run_ln(h, h->ds_ln[i], xb, ln, M, s));
       ConvCall cd = pointwise(ln, M);
       cd.y = xb;
       RUN(run_conv(h, h->ds_conv[i], cd, s));
     }
-    for (auto& bw : h->blocks[i]) RUN(run_block(h, bw, xb, nullptr, B, T, ln, hid, s, 0, rg));
+    for (auto& bw : h->blocks[i]) RUN(run_block(h, bw, xb, nullptr, B, T, ln, hid, s, LAYOUT_PLANES, rg));
   }
   RUN(run_ln(h, h->enc_norm, xb, feat, M, s));  // an h2 feat: row-scaled into feat.row_ash
   return DCX_OK;
@@ -191,13 +190,13 @@ int stage_encode(dcx_codec* h, CAct mel, int B, int T, Act feat, Bump& ws, hipSt
       });
 }
 
-// x_pjt_in layout the nearest-code search reads (ConvParams::x_compact): 1 compact bf16 for
-// vq_prefilter_b1 (x6 and bf16 modes), else 0 planes (vq_prefilter_dm / _x3; fp32 mode ignores it).
-int vq_xlayout(const dcx_codec* h) { return x6_mode(h) && h->compact && h->codebook_b1 ? 1 : 0; }
+// x_pjt_in layout the nearest-code search reads: compact bf16 for vq_prefilter_b1 (x6 and bf16
+// modes), else planes (vq_prefilter_dm / _x3; fp32 mode ignores it).
+Layout vq_xlayout(const dcx_codec* h) { return x6_mode(h) && h->compact && h->codebook_b1 ? LAYOUT_BF16 : LAYOUT_PLANES; }
 
 // The nearest-code search of DownsampleGRVQ (vector_quantize_pytorch.py:41-45, 496-506; first index on
-// ties) on x_pjt_in P (fp32 [M][CD]) and, in x6 / bf16 mode, P6 in the prefilter's layout xl (0 planes,
-// 1 compact bf16): |x|^2, the certified prefilter and the fp64 rescore (x6 / bf16), or the exact
+// ties) on x_pjt_in P (fp32 [M][CD]) and, in x6 / bf16 mode, P6 in the prefilter's layout xl (planes or
+// compact bf16): |x|^2, the certified prefilter and the fp64 rescore (x6 / bf16), or the exact
 // fp32 distance GEMM and its reduce (fp32 mode).  pv / pi / pv2: [M][ntiles] scratch, x2: [M].
 // Workspace of one search of M rows: the prefilter's [M][ntiles] partials and, in x6 / bf16 mode, the
 // rescore's candidate list (128 pairs per row on average: the C2 workload lists 62 in x6 mode; a row that does not fit is rescored in place).
@@ -223,12 +222,12 @@ VqScratch vq_scratch(const dcx_codec* h, Bump& ws, long long M, int ntiles, bool
   return v;
 }
 
-int run_vq_search(dcx_codec* h, const float* P, const unsigned short* P6, int xl, long long M, const VqScratch& v,
+int run_vq_search(dcx_codec* h, const float* P, const unsigned short* P6, Layout xl, long long M, const VqScratch& v,
                   int ntiles, int32_t* codes, hipStream_t s) {
   const dcx_config& c = h->cfg;
   const int CD = c.codebook_dim, NC = c.codebook_size;
   const bool x6 = x6_mode(h);
-  const bool b1 = xl == 1 && dcx::vq_b1_takes(NC, CD);
+  const bool b1 = xl == LAYOUT_BF16 && dcx::vq_b1_takes(NC, CD);
   float* const x2 = v.x2;
   LAUNCH(h, s, "row_sqnorm", 2.0 * M * CD, 4.0 * M * CD,
          dcx::launch_row_sqnorm(P, M, CD, x2, x6 ? v.x2d : nullptr, b1 ? v.xr2 : nullptr, x6 ? v.npairs : nullptr, s));
@@ -237,7 +236,7 @@ int run_vq_search(dcx_codec* h, const float* P, const unsigned short* P6, int xl
     p.x = P; p.x6 = P6; p.w = h->codebook; p.w6 = x6 ? h->codebook6 : nullptr;
     p.Cin = CD; p.Cout = NC; p.ldx = CD; p.taps = 1; p.in_step = 1; p.out_mul = 1;
     p.x2 = x2; p.e2 = h->e2; p.part_val = v.pv; p.part_idx = v.pi; p.part_val2 = v.pv2;
-    p.x_compact = xl;
+    p.x_layout = xl;
     p.wc = b1 ? h->codebook_b1 : nullptr;
     ProfScope ps(h, s);
     const char* kname = "vq";
@@ -295,16 +294,13 @@ int stage_vq_encode(dcx_codec* h, CAct feat, int B, int T, int32_t* codes, float
   const long long M = (long long)B * T;
   const int D = c.vq_dim, CD = c.codebook_dim, NC = c.codebook_size;
   const bool x6 = x6_mode(h);
-  const int xl = vq_xlayout(h);
+  const Layout xl = vq_xlayout(h);
   const int ntiles = x6 ? dcx::vq_prefilter_ntiles(NC, CD, xl) : dcx::vq_argmin_ntiles(NC);
   // the down conv's input as the fused pipeline writes it: compact bf16 (bf16 mode) or h2 (h3), the
   // latter scaled per row by the row's exact max as the encoder's final LayerNorm scales it, so the
   // staged and the fused call compute the same bits
-  {
-    const bool cmp = takes_compact(h, h->vq_down, M);
-    RUN(ensure_planes(h, feat, M, D, ws, s, cmp, !cmp && takes_h3(h, h->vq_down), 0));
-  }
-  if (feat.c1 && !takes_compact(h, h->vq_down, M)) return fail(h, DCX_ERR_STATE, "internal: compact features");
+  RUN(ensure_planes(h, feat, M, D, ws, s, input_layout(h, h->vq_down, M), 0));
+  if (feat.lay == LAYOUT_BF16 && !takes_compact(h, h->vq_down, M)) return fail(h, DCX_ERR_STATE, "internal: compact features");
   float* X = ws.f((size_t)M * D);
   unsigned short* X6 = x6 ? ws.u16((size_t)M * D * 3) : nullptr;
   Act ln = conv_input(h, ws, (size_t)M * D);
@@ -319,19 +315,18 @@ int stage_vq_encode(dcx_codec* h, CAct feat, int B, int T, int32_t* codes, float
   ConvCall cd = pointwise(feat, M);
   cd.y = X;
   RUN(run_conv(h, h->vq_down, cd, s));
-  const bool x6c = X6 && takes_compact(h, h->vq_pin, M);
-  const bool h2p = X6 && !x6c && takes_h3(h, h->vq_pin);  // project_in on conv_gemm_x3dw
+  const Layout xp = X6 ? input_layout(h, h->vq_pin, M) : LAYOUT_PLANES;
+  const bool h2p = xp == LAYOUT_H2;  // project_in on conv_gemm_x3dw
   // the block's output for project_in: compact / planes from its epilogue, or (h3) split per row by
   // the row's exact max afterwards (launch_h2_rows)
-  RUN(run_block(h, h->vq_down_blk, X, h2p ? nullptr : X6, B, T, ln, hid, s, x6c ? 1 : 0, rg));
+  RUN(run_block(h, h->vq_down_blk, X, h2p ? nullptr : X6, B, T, ln, hid, s, xp, rg));
   if (h2p) LAUNCH(h, s, "h2_rows", 0, 8.0 * M * D, dcx::launch_h2_rows(X, X6, M, D, x6_ash, s));
-  CAct pin_in(X, X6, x6c);
-  pin_in.h2 = h2p;
+  CAct pin_in(X, X6, xp);
   if (h2p) pin_in.r.ash_row = x6_ash;
   ConvCall cp = pointwise(pin_in, M);
   cp.y = P;
   cp.y6 = P6;
-  cp.y6c = xl;
+  cp.y_lay = xl;
   RUN(run_conv(h, h->vq_pin, cp, s));
   RUN(run_vq_search(h, P, P6, xl, M, vs, ntiles, codes, s));
   if (fup) LAUNCH(h, s, "gather_rows", 0, 8.0 * M * CD, dcx::launch_gather_rows(h->codebook, NC, codes, M, CD, fup, nullptr, -1, s));
@@ -340,7 +335,7 @@ int stage_vq_encode(dcx_codec* h, CAct feat, int B, int T, int32_t* codes, float
     ConvCall cu = pointwise(zd, M);
     cu.y = quant;
     RUN(run_conv(h, h->vq_up, cu, s));
-    RUN(run_block(h, h->vq_up_blk, quant, nullptr, B, T, ln, hid, s, 0, rg));
+    RUN(run_block(h, h->vq_up_blk, quant, nullptr, B, T, ln, hid, s, LAYOUT_PLANES, rg));
   }
   return DCX_OK;
 }
@@ -356,7 +351,7 @@ int stage_vq_decode(dcx_codec* h, const int32_t* codes, int B, int T, Act z, int
   Act hid = conv_input(h, ws, (size_t)M * 4 * D);
   row_ranges(h, ws, M, ln, hid);
   WS_READY(h, ws, "workspace too small for vq_decode");
-  if (z.p && z.h2) return fail(h, DCX_ERR_STATE, "internal: z in h2 is split by the generator (ranged per clip)");
+  if (z.p && z.lay == LAYOUT_H2) return fail(h, DCX_ERR_STATE, "internal: z in h2 is split by the generator (ranged per clip)");
   RUN(gather_decoded(h, codes, M, zd, n_invalid, s, lens, T));
   ConvCall cu = pointwise(zd, M);
   cu.y = z.f;
@@ -389,11 +384,11 @@ static int encode_clips_to_z(dcx_codec* h, const float* audio, int B, int64_t n,
   const long long M = (long long)B * T;
   Act mel = conv_input(h, ws, (size_t)M * c.n_mels);
   Act feat = conv_input(h, ws, (size_t)M * c.enc_dims[3]);
-  feat.c1 = feat.p && takes_compact(h, h->vq_down, M);  // written by the encoder's final LayerNorm
-  feat.h2 = feat.p && !feat.c1 && takes_h3(h, h->vq_down);  // h2 for the quantizer's down conv (x3dw)
+  // written by the encoder's final LayerNorm: compact (bf16 mode), or h2 for the quantizer's down conv (x3dw)
+  feat.lay = input_layout(h, h->vq_down, M);
   // (reserved whenever x6 mode could write it: a dry run sees no pointers, so sizes must not depend on them)
   if (x6_mode(h)) feat.row_ash = ws.i((size_t)M);
-  if (feat.h2) feat.r.ash_row = feat.row_ash;  // scaled per row by the final LayerNorm (its exact row maxima)
+  if (feat.lay == LAYOUT_H2) feat.r.ash_row = feat.row_ash;  // scaled per row by the final LayerNorm (its exact row maxima)
   const size_t mark = ws.off;
   size_t need = mark;
   auto sub = [&](auto fn) -> int {  // each sub-stage reuses the tail of the workspace
@@ -420,10 +415,9 @@ int tokenize_ragged_rows(dcx_codec* h, const float* audio, const dcx::RaggedSeg&
   const long long M = rg.rows;
   Act mel = conv_input(h, ws, (size_t)M * c.n_mels);
   Act feat = conv_input(h, ws, (size_t)M * c.enc_dims[3]);
-  feat.c1 = feat.p && takes_compact(h, h->vq_down, M);
-  feat.h2 = feat.p && !feat.c1 && takes_h3(h, h->vq_down);
+  feat.lay = input_layout(h, h->vq_down, M);
   if (x6_mode(h)) feat.row_ash = ws.i((size_t)M);
-  if (feat.h2) feat.r.ash_row = feat.row_ash;
+  if (feat.lay == LAYOUT_H2) feat.r.ash_row = feat.row_ash;
   const size_t mark = ws.off;
   size_t need = mark;
   auto sub = [&](auto fn) -> int {  // each sub-stage reuses the tail of the workspace

@@ -424,7 +424,7 @@ static int build_all(dcx_codec* h, Builder& B, int32_t with_generator) {
       int rc = run_conv(h, pout, cp, 0, /*force_f32=*/true);
       if (rc != DCX_OK) return rc;
       if (hipMemcpy(h->ptable + (size_t)NC * D, pout.b, sizeof(float) * D, hipMemcpyDeviceToDevice) != hipSuccess ||
-          dcx::launch_split_planes(h->ptable, h->ptable6, NC + 1, D, 0, 0) != hipSuccess ||
+          dcx::launch_split_planes(h->ptable, h->ptable6, NC + 1, D, LAYOUT_PLANES, 0) != hipSuccess ||
           hipDeviceSynchronize() != hipSuccess)
         return fail(h, DCX_ERR_HIP, "decode-table build failed");
     }
@@ -441,7 +441,7 @@ static int build_all(dcx_codec* h, Builder& B, int32_t with_generator) {
         hipFree(tmp);
         return fail(h, DCX_ERR_OOM, "hipMalloc failed");
       }
-      int rc = dcx::launch_split_planes(h->codebook, e6, NC, CD, 0, 0) == hipSuccess
+      int rc = dcx::launch_split_planes(h->codebook, e6, NC, CD, LAYOUT_PLANES, 0) == hipSuccess
                    ? DCX_OK : fail(h, DCX_ERR_HIP, "codebook split failed");
       const int mode = h->gemm_mode;
       h->gemm_mode = DCX_GEMM_BF16;
@@ -451,7 +451,7 @@ static int build_all(dcx_codec* h, Builder& B, int32_t with_generator) {
       h->gemm_mode = mode;
       if (rc == DCX_OK &&
           (hipMemcpy(tmp + (size_t)NC * D, pout.b16, sizeof(float) * D, hipMemcpyDeviceToDevice) != hipSuccess ||
-           dcx::launch_split_planes(tmp, h->ptable6b, NC + 1, D, 0, 0) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
+           dcx::launch_split_planes(tmp, h->ptable6b, NC + 1, D, LAYOUT_PLANES, 0) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
         rc = fail(h, DCX_ERR_HIP, "bf16 decode-table build failed");
       hipFree(e6);
       hipFree(tmp);
