@@ -3,6 +3,7 @@
 #include "dcx_conv_common.h"
 #include "dcx_conv_launch.h"
 #include "dcx_conv_pingpong.h"
+#include "dcx_a3_layout.h"
 #include "dcx_w3_layout.h"
 
 namespace dcx {
@@ -209,7 +210,7 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_x3dq_group(const ConvGroup g
 // the end of MEM1(s + 1), before the barrier that opens MEM0(s + 1), their first reader.
 // BN = 256: 256 x 256 tiles of 64 x 128 wave tiles (Cout % 256 == 0); BN = 128: 384 x 128 tiles of
 // 48 x 128 wave tiles (the C = 128 stage: 72 MFMAs per segment against x3dq's 48).
-template <int HALO, bool SPLIT, int BN = 256, bool RAG = false>
+template <int HALO, bool SPLIT, int BN = 256, bool RAG = false, bool GROUPED = false>
 __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams& pr, const int wg, const int b, const int ph) {
   constexpr int BM = BN == 256 ? 256 : 384, WN = BN / 128, WM = 8 / WN;
   constexpr int WR = BM / WM, WC = 128, TM = WR / 16, TN = WC / 16;
@@ -251,12 +252,22 @@ __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams&
   const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc(
       (void*)(p.w3 + w3_step(taps, p.Cin, p.Cout, ph, 0, 0)), 0, taps * nchunks * p.Cout * 128, 0x00020000);
 
-  // DMA (group 0 alone): instruction k fills 64 rows of piece (k * 64) / rows; the wave's i-th is
-  // k = i * 4 + gw.  Lane part of the source offset in one VGPR, the rest wave-uniform.  (Group 1
+  // The A image: rows of 128 B with XOR-permuted pieces, fetched 8 rows per instruction
+  // (dcx_a3_layout.h).  One instantiation keeps x3dq's piece-major image, [piece 8][AR][16 B], 64 rows
+  // of one piece per instruction: conv_gemm_x3dw's unsplit, unragged halo form at BN = 256 (launched
+  // under DCX_H3_SPLIT=0 only), whose epilogue spills 8 bytes more with the row image's DMA offsets
+  // in place (12 -> 20, profiles/a3_image_resources.md), whatever their spelling.  The grouped kernel
+  // calls this function with the same HALO / SPLIT / BN / RAG and takes the row image (GROUPED).
+  constexpr bool ROWS = !(HALO && !SPLIT && BN == 256 && !RAG && !GROUPED);
+  // DMA (group 0 alone): A instruction k fills image rows [8 k, 8 k + 8) with their chunks, 128 B per 8
+  // lanes; B instruction k fills 64 columns of piece (k * 64) / BN; the wave's i-th is k = i * 4 + gw.
+  // Lane part of the source offset in one VGPR, the rest wave-uniform; both go into the vector offset
+  // (the scalar one stays 0): a negative row's lane part must wrap together with the uniform part
+  // before the descriptor's range check, or the row would not read zeros.  (Group 1
   // issuing half of the weight pieces from inside its MFMA segment, so that the DMA of a step is in
   // flight in both segments, measured slower: C2 194.2-194.7 against 185.3-185.4 ms, r05n; the
   // issue stalls behind group 0's and holds up the MFMAs.)
-  const int a_lane = (rbase + lane) * arow;  // negative rows: huge unsigned, out of range (zeros)
+  const int a_lane = ROWS ? a3_src_lane(rbase, arow, lane) : (rbase + lane) * arow;  // negative rows: huge unsigned, out of range (zeros)
   const int b_lane = w3_wide_lane(co0, lane);  // dcx_w3_layout.h: every weight piece is 1 KiB contiguous
   [[maybe_unused]] bool in_loop = false;  // -DDCX_X3_NODMA (diagnostic): no DMA after the prologue (wrong results)
   auto dmaA1 = [&](int c, int slot, int i) {  // the wave's i-th A piece of chunk c
@@ -264,9 +275,13 @@ __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams&
     if (in_loop) return;
 #endif
     const int k = i * 4 + gw;
-    const int u = k * 64, pc = u / AR, row = u - pc * AR;
     const int abuf = HALO ? (c & 1) : slot;
-    dma16(rx, lds + abuf * (ABUF / 2) + k * 512, a_lane + row * arow + (pc & 3) * 32 + (pc >> 2) * 16 + c * 128, 0);
+    if constexpr (ROWS) {
+      dma16(rx, lds + abuf * (ABUF / 2) + k * 512, a_lane + a3_src_inst(arow, k, c), 0);
+    } else {
+      const int u = k * 64, pc = u / AR, row = u - pc * AR;
+      dma16(rx, lds + abuf * (ABUF / 2) + k * 512, a_lane + row * arow + (pc & 3) * 32 + (pc >> 2) * 16 + c * 128, 0);
+    }
   };
   // B instructions [0, B_G0) are group 0's, [B_G0, B_N) group 1's (SPLIT)
 #ifndef DCX_X3W_BG0_DIV  // A/B builds: group 0's share of the weight pieces, 1 / DIV (halo convs)
@@ -295,14 +310,20 @@ __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams&
   };
 
   // fragment addresses: one lane base per operand (h piece of the lane's channel group kg); the
-  // l piece, row / column blocks and the B slot are immediate offsets
+  // l piece of B, row / column blocks and the B slot are immediate offsets.  The A image
+  // (dcx_a3_layout.h) is not linear in the row, so a tap conv's base is recomputed per step from the
+  // lane's row; its l piece is the h address ^ 64.
   const int l15 = lane & 15, kg = lane >> 4;
   const char* const ldsb = reinterpret_cast<const char*>(lds);
-  const char* const a_rd = ldsb + kg * AR * 16 + (wm * WR + l15) * 16;
+  const int a_row = wm * WR + l15;  // image row of the lane's first fragment at tap offset 0
+  static_assert(WR % kA3BlockRows == 0 && a3_image(16, 0) == 2048, "row blocks as immediates");
   const char* const b_rd = ldsb + NA * ABUF + kg * BN * 16 + (wn * WC + l15) * 16;
   s16x8 aq[TM][2], bq[TN][2];  // [h, l]
   auto readF = [&](int c, int m, int slot) {
-    const char* a = a_rd + ((HALO ? (c & 1) : slot) * ABUF + (m * p.in_step - lo_rel) * 16);
+    const int a_r = a_row + (HALO ? m * p.in_step - lo_rel : 0);
+    const int ah = (HALO ? (c & 1) : slot) * ABUF + (ROWS ? a3_image(a_r, kg) : kg * AR * 16 + a_r * 16);
+    const char* a = ldsb + ah;
+    const char* al = ldsb + (ROWS ? ah ^ kA3PlaneXor : ah + 4 * AR * 16);
     const char* bb = b_rd + slot * BBUF;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -311,8 +332,8 @@ __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams&
     }
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
-      aq[i][0] = *reinterpret_cast<const s16x8*>(a + i * 256);
-      aq[i][1] = *reinterpret_cast<const s16x8*>(a + i * 256 + 4 * AR * 16);
+      aq[i][0] = *reinterpret_cast<const s16x8*>(a + i * (ROWS ? 2048 : 256));
+      aq[i][1] = *reinterpret_cast<const s16x8*>(al + i * (ROWS ? 2048 : 256));
     }
   };
   f32x4 acc[TM][TN];
@@ -448,7 +469,7 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_x3dw_group(const ConvGroup g
   ConvParams p;
   int local, b;
   const ConvParams& pr = group_member(g, p, local, b);
-  x3dw_tile<64, SPLIT, BN, RAG>(p, pr, local, b, 0);
+  x3dw_tile<64, SPLIT, BN, RAG, true>(p, pr, local, b, 0);
 }
 
 // Whether conv_gemm_x3dq<bn> (taps >= 3 with a halo) or conv_gemm_x3dm<bn> (one tap) takes an h3

@@ -7,8 +7,12 @@
 //   c  1 KiB contiguous
 //   d  8 rows x 128 B at 2 KiB stride
 //   e  16 runs x 64 B at 128 B stride
+//   f  d's 8 rows x 128 B, rows fastest over the lanes: lane j takes piece j >> 3 of row j & 7
+//   g  d with the 8 pieces of a row XOR-permuted: lane j takes piece (j & 7) ^ (((r >> 1) & 3) << 1) of row r = j >> 3
+//      (f and g: the two lane orders of conv_gemm_x3dw's activation image, csrc/dcx_a3_layout.h; a
+//      piece q = plane * 4 + channel group lies at (q & 3) * 32 + (q >> 2) * 16 of the row's 128 B)
 // In every shape consecutive pieces of a wave walk one block (a: the 8 pieces of 64 columns, b: the
-// 128 of 64 rows, d: the 16 of 8 rows, e: the 2 of 16 runs), so each covers the buffer once per
+// 128 of 64 rows, d, f, g: the 16 of 8 rows, e: the 2 of 16 runs), so each covers the buffer once per
 // sweep.  The buffer is 2 MiB (resident in every XCD's L2; every workgroup reads all of it) or
 // 2 GiB (streamed: every byte is read once per run).  It only measures: every offset is taken modulo the buffer's size, under a
 // descriptor of exactly that size, and the iteration count is fixed.
@@ -34,20 +38,23 @@ constexpr int kRing = 64 * 1024;  // bytes
   } while (0)
 
 // lane part and (wave-uniform) piece part of the source offset of piece P
+__device__ __forceinline__ unsigned h2_piece(int q) { return (q & 3) * 32 + (q >> 2) * 16; }
 template <int SHAPE>
 __device__ __forceinline__ unsigned lane_off(int lane) {
   if constexpr (SHAPE == 0) return lane * 128;
   else if constexpr (SHAPE == 1) return lane * 2048;
   else if constexpr (SHAPE == 2) return lane * 16;
   else if constexpr (SHAPE == 3) return (lane >> 3) * 2048 + (lane & 7) * 16;
-  else return (lane >> 2) * 128 + (lane & 3) * 16;
+  else if constexpr (SHAPE == 4) return (lane >> 2) * 128 + (lane & 3) * 16;
+  else if constexpr (SHAPE == 5) return (lane & 7) * 2048 + h2_piece(lane >> 3);
+  else return (lane >> 3) * 2048 + h2_piece((lane & 7) ^ (((lane >> 4) & 3) << 1));
 }
 template <int SHAPE>
 __device__ __forceinline__ unsigned piece_off(unsigned P) {
   if constexpr (SHAPE == 0) return (P >> 3) * 8192 + (P & 3) * 32 + ((P >> 2) & 1) * 16;
   else if constexpr (SHAPE == 1) return (P >> 7) * 131072 + (P & 127) * 16;
   else if constexpr (SHAPE == 2) return P * 1024;
-  else if constexpr (SHAPE == 3) return (P >> 4) * 16384 + (P & 15) * 128;
+  else if constexpr (SHAPE == 3 || SHAPE >= 5) return (P >> 4) * 16384 + (P & 15) * 128;
   else return (P >> 1) * 2048 + (P & 1) * 64;
 }
 
@@ -105,10 +112,11 @@ int main() {
   CHECK(hipMemset(buf, 1, big));
   CHECK(hipMalloc(&out, (size_t)cus * 512 * sizeof(float)));
   CHECK(hipMalloc(&cyc, (size_t)cus * sizeof(unsigned long long)));
-  const kern_t kerns[2][5] = {{k<0, false>, k<1, false>, k<2, false>, k<3, false>, k<4, false>},
-                              {k<0, true>, k<1, true>, k<2, true>, k<3, true>, k<4, true>}};
-  const char* names[5] = {"a 64 x 16 B / 128 B", "b 64 x 16 B / 2 KiB", "c 1 KiB contiguous", "d 8 x 128 B / 2 KiB",
-                          "e 16 x 64 B / 128 B"};
+  constexpr int kShapes = 7;
+  const kern_t kerns[2][kShapes] = {{k<0, false>, k<1, false>, k<2, false>, k<3, false>, k<4, false>, k<5, false>, k<6, false>},
+                                    {k<0, true>, k<1, true>, k<2, true>, k<3, true>, k<4, true>, k<5, true>, k<6, true>}};
+  const char* names[kShapes] = {"a 64 x 16 B / 128 B", "b 64 x 16 B / 2 KiB", "c 1 KiB contiguous", "d 8 x 128 B / 2 KiB",
+                                "e 16 x 64 B / 128 B", "f d, rows fastest", "g d, pieces XOR-ed"};
   const int iters = 128, reps = 7;  // 8 MiB per CU and run
   std::vector<unsigned long long> hc(cus);
   hipEvent_t e0, e1;
@@ -119,7 +127,7 @@ int main() {
   printf("%-8s %-5s %-22s %8s %8s %8s   %8s %8s\n", "buffer", "mfma", "shape", "B/c min", "B/c med", "B/c max", "GB/s med", "cyc/grp");
   for (int sz = 0; sz < 2; ++sz)
     for (int mf = 0; mf < 2; ++mf)
-      for (int sh = 0; sh < 5; ++sh) {
+      for (int sh = 0; sh < kShapes; ++sh) {
         const unsigned bytes = (unsigned)(sz ? big : small);
         std::vector<double> bpc, gbs;
         for (int rep = -1; rep < reps; ++rep) {  // run -1 warms up
