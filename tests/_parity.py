@@ -76,3 +76,40 @@ def check_wave(eng, gpu_codes, ref_codes, gpu_wav, ref_wav, min_db: float) -> fl
     snr = snr_db(wav, ref_wav)
     assert snr >= min_db, f"waveform SNR {snr:.1f} dB < {min_db} dB (codes identical: {np.array_equal(gc, rc)})"
     return snr
+
+
+# ---------------------------------------------------------------------------------------------
+# The ragged batches of tests/test_gpu_ragged_scale.py and tests/test_ragged_plan.py: one pool of
+# 19 short clips and a 10 s filler, repeated and shuffled so that every dwconv_ln form of
+# launch_dwconv_ln_ragged is selected once.
+# ---------------------------------------------------------------------------------------------
+# Frame counts below the 7-row window and the ring's prefetch distance, then just below, at and just
+# above the 4-, 8-, 16- and 32-row widths: 376 frames, 33 16-row tiles.
+RAGGED_SHORT_T = [1, 2, 3, 4, 5, 6, 7, 8, 9, 11, 15, 16, 17, 31, 32, 33, 47, 64, 65]
+RAGGED_LONG_N, RAGGED_LONG_T = 240000, 937
+# case -> (copies of the short set, copies of the long clip, total frames, form); form 0: 16-row tiles
+# (>= 512 of them below 8192 rows), else the register ring's run width (8192 * {1, 2, 4, 8} rows)
+RAGGED_CASES = {
+    "t16": (20, 0, 7520, 0),
+    "rw4": (22, 0, 8272, 4),
+    "rw8": (22, 9, 16705, 8),
+    "rw16": (22, 27, 33571, 16),
+    "rw32": (22, 62, 66366, 32),
+}
+
+
+def ragged_pool_lengths() -> list[int]:
+    """Raw sample counts of the pool, the long clip last.  A clip of n samples has 1 + (n + 1 - 256) // 256
+    frames (n + 1 >= 385), so T frames come from 256 T - 1 .. 256 T + 254 samples: even short clips
+    take the low end (384 at T = 1, the shortest the reflect pad accepts), odd ones the high end."""
+    n = [max(384, 256 * t - 1) if i % 2 == 0 else 256 * t + 254 for i, t in enumerate(RAGGED_SHORT_T)]
+    return n + [RAGGED_LONG_N]
+
+
+def ragged_case_order(case: str) -> np.ndarray:
+    """Pool indices of a case's clips in batch order: the pool repeated, then shuffled with a fixed
+    seed, so long and short clips alternate and a workgroup's four runs fall in different clips."""
+    k_short, k_long, _, _ = RAGGED_CASES[case]
+    ns = len(RAGGED_SHORT_T)
+    idx = np.concatenate([np.tile(np.arange(ns), k_short), np.full(k_long, ns, dtype=np.int64)])
+    return np.random.default_rng(7000 + k_long).permutation(idx)

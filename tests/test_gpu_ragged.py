@@ -4,9 +4,13 @@ ALONE.  The reference for a clip is therefore the CPU oracle on that clip alone 
 never on the padded batch.
 
 Set A: raw lengths 400, 700, 1800, 4300, 8500, 30000 -> 1, 2, 7, 16, 33, 117 frames (shorter than the k7
-halo, equal to the kernel size, across a 16-row tile edge, long); 176 rows: the tiled dwconv_ln kernel.
-Set B: 24 clips of 80000 + 1111 i samples, 8684 rows (the sum of dcx_num_frames(n + 1)): the register-ring
-kernel (>= 8192 rows).
+halo, equal to the kernel size, at and across several 4-row tile edges, long); 176 rows in 15 16-row
+tiles, fewer than 512: dwconv_ln_seg_kernel<NV, 4>, the 4-row tiles.  No clip here meets a 16-row tile.
+Set B: 24 clips of 80000 + 1111 i samples (312 .. 412 frames each), 8684 rows (the sum of
+dcx_num_frames(n + 1)): dwconv_ln_run_seg_kernel<NV, 4, D>, the register ring at run width 4 (8192 ..
+16383 rows).
+The 16-row tiles (dwconv_ln_seg_kernel<NV, 16>), the run widths 8, 16 and 32, and clips shorter than a
+run or the ring's window inside such batches are in tests/test_gpu_ragged_scale.py.
 
 Tolerances: codes exact on decisive frames (fp64 relative top-2 gap > 1e-4) and >= 97 % overall
 (tests/_parity.py); x_pjt_in max relative error < 2e-4 (the bound of tests/test_gpu_stages.py).  bf16

@@ -83,6 +83,77 @@ def test_plan_of_a_permutation_is_the_permuted_plan(handle):
     assert np.array_equal(p0[:head], p1[:head])  # the totals do not depend on the order
 
 
+def _ceil(a, d):
+    return [-(-x // d) for x in a]
+
+
+def _check_plan_at_scale(L, h, lengths, frames, rw):
+    """The table of a large batch: the five prefix arrays' per-clip differences are the clip's samples,
+    T, ceil(T / 16), ceil(T / 4) and ceil(T / rw) (as a multiset: at rw = 4 two of them coincide), the
+    totals are their last entries, and the header holds exactly those totals, the clip count and rw."""
+    B = len(lengths)
+    rc, plan, ts, tf = _plan(L, h, lengths)
+    assert rc == 0, L.dcx_last_error(h)
+    assert (plan != -7).all()
+    assert ts == sum(lengths) and tf == sum(frames)
+    arrs = _prefix_arrays(plan, B)
+    assert arrs.shape == (5, B + 1)
+    want = [list(lengths), list(frames), _ceil(frames, 16), _ceil(frames, 4), _ceil(frames, rw)]
+    assert sorted(np.diff(a).tolist() for a in arrs) == sorted(want)
+    totals = sorted(int(a[-1]) for a in arrs)
+    assert totals == sorted(sum(w) for w in want)
+    head = plan[: plan.shape[0] - arrs.size]
+    assert sorted(head[1:].tolist()) == sorted(totals + [B, rw]), head  # head[0]: the table's tag
+    return plan
+
+
+@pytest.mark.parametrize("case", ["t16", "rw4", "rw8", "rw16", "rw32"])
+def test_plan_at_scale(handle, case):
+    """One total in each row class of launch_dwconv_ln_ragged, the batches of tests/test_gpu_ragged_scale.py:
+    run width 4 / 8 / 16 / 32 from 8192 * {1, 2, 4, 8} rows (4 below: the tiled forms do not read it)."""
+    from _parity import RAGGED_CASES, RAGGED_LONG_T, RAGGED_SHORT_T, ragged_case_order, ragged_pool_lengths
+
+    L, h = handle
+    pool_n, pool_t = ragged_pool_lengths(), RAGGED_SHORT_T + [RAGGED_LONG_T]
+    assert [int(L.dcx_num_frames(h, n + 1)) for n in pool_n] == pool_t
+    assert sum(RAGGED_SHORT_T) == 376 and sum(_ceil(RAGGED_SHORT_T, 16)) == 33
+    k_short, k_long, total, form = RAGGED_CASES[case]
+    order = ragged_case_order(case)
+    assert len(order) == 19 * k_short + k_long
+    lengths, frames = [pool_n[i] for i in order], [pool_t[i] for i in order]
+    assert sum(frames) == total
+    rw = 32 if total >= 65536 else 16 if total >= 32768 else 8 if total >= 16384 else 4
+    assert rw == (form or 4) and (form == 0) == (total < 8192)
+    if form == 0:
+        assert sum(_ceil(frames, 16)) >= 512  # the 16-row tiles, not the 4-row ones
+    # long and short clips alternate: no stretch of the batch is all of one kind
+    if k_long:
+        is_long = np.asarray(frames) == RAGGED_LONG_T
+        assert 0 < is_long[: len(frames) // 2].sum() < k_long
+    _check_plan_at_scale(L, h, lengths, frames, rw)
+
+
+@pytest.mark.parametrize("case,total,rw", [("t16", 8191, 4), ("t16", 8192, 4), ("rw4", 16383, 4), ("rw4", 16384, 8),
+                                           ("rw8", 32767, 8), ("rw8", 32768, 16), ("rw16", 65535, 16),
+                                           ("rw16", 65536, 32)])
+def test_plan_at_class_boundaries(handle, case, total, rw):
+    """The last total of a row class and the first of the next, reached by adding 1-frame clips
+    (384 samples) to one of the compositions above."""
+    from _parity import RAGGED_CASES, RAGGED_LONG_T, RAGGED_SHORT_T, ragged_case_order, ragged_pool_lengths
+
+    L, h = handle
+    pool_n, pool_t = ragged_pool_lengths(), RAGGED_SHORT_T + [RAGGED_LONG_T]
+    order = ragged_case_order(case)
+    extra = total - RAGGED_CASES[case][2]
+    assert extra > 0
+    lengths = [pool_n[i] for i in order] + [384] * extra
+    frames = [pool_t[i] for i in order] + [1] * extra
+    assert sum(frames) == total
+    plan = _check_plan_at_scale(L, h, lengths, frames, rw)
+    assert int(L.dcx_ragged_workspace_size(h, len(lengths), total)) > 0
+    assert plan.shape[0] == int(L.dcx_ragged_plan_size(len(lengths)))
+
+
 def test_plan_validation(handle):
     from distilcodec_nabeel_amd import _native
 
