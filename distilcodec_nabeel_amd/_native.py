@@ -73,6 +73,8 @@ SIGNATURES = {
     "dcx_build_id": (ctypes.c_char_p, []),
     "dcx_set_tensor": (ctypes.c_int, [_P, ctypes.c_char_p, _P, _I32, ctypes.POINTER(_I64)]),
     "dcx_finalize": (ctypes.c_int, [_P, _I32]),
+    "dcx_set_num_codebooks": (ctypes.c_int, [_P, _I32]),
+    "dcx_num_codebooks": (_I32, [_P]),
     "dcx_num_frames": (_I64, [_P, _I64]),
     "dcx_workspace_size": (_SZ, [_P, _I32, _I64]),
     "dcx_mel": (ctypes.c_int, [_P, _P, _I32, _I64, _P, _P, _SZ, _P]),

@@ -52,6 +52,12 @@ class AttrDict(dict):
         self.__dict__ = self
 
 
+def _gbtr(codes: torch.Tensor) -> torch.Tensor:
+    """Engine codes (B, T) or (B, T, R) -> the reference's (G=1, B, T, R) int64 layout."""
+    c = codes.long()
+    return c[None, :, :, None] if c.ndim == 2 else c[None]
+
+
 def _cf(x: torch.Tensor) -> torch.Tensor:
     """channels-last (B, T, C) storage -> the reference's (B, C, T) view."""
     return x.transpose(1, 2)
@@ -98,25 +104,26 @@ class Quantizer(_Part):
     def __call__(self, encoded_feature: torch.Tensor) -> GRVQResult:
         codes, pin, fup, q = self._eng.vq_encode(_cf(encoded_feature))
         zero = torch.zeros((), device=codes.device)
-        return GRVQResult(quantized=_cf(q), codes=codes.long()[None, :, :, None], codes_list=[], total_loss=zero,
+        return GRVQResult(quantized=_cf(q), codes=_gbtr(codes), codes_list=[], total_loss=zero,
                           commitment_loss=zero.clone(), codebook_diversity_loss=zero.clone(), quantized_fup=fup,
                           quantized_fup_list=[], x_pjt_in=pin, x_pjt_in_list=[])
 
     forward = __call__
 
     def encode(self, encoded_feature: torch.Tensor) -> torch.Tensor:
-        """grfvq.py:134-139: indices rearranged 'g b l r -> b (g r) l' -> (B, 1, T) int64."""
+        """grfvq.py:134-139: indices rearranged 'g b l r -> b (g r) l' -> (B, R, T) int64."""
         codes, *_ = self._eng.vq_encode(_cf(encoded_feature), want_pjt_in=False, want_fup=False, want_quantized=False)
-        return codes.long()[:, None, :]
+        return _gbtr(codes)[0].transpose(1, 2).contiguous()
 
     def decode(self, indices: torch.Tensor) -> torch.Tensor:
-        """grfvq.py:141-146 with indices (G=1, B, T, R=1) -> (B, 1024, T).  Like the reference, a
-        (B, 1, T, 1) tensor is read with dim 0 as the group axis (get_output_from_indices zips
+        """grfvq.py:141-146 with indices (G=1, B, T, R) -> (B, 1024, T).  Like the reference, a
+        (B, 1, T, R) tensor is read with dim 0 as the group axis (get_output_from_indices zips
         groups over dim 0, residual_vq.py:301-303), i.e. only clip 0 of it is decoded."""
         idx = torch.as_tensor(indices)
-        if idx.ndim != 4 or idx.shape[-1] != 1:
-            raise ValueError("indices must be laid out (groups=1, batch, frames, residuals=1)")
-        codes = idx[0, :, :, 0]
+        R = self._codec.nresiduals
+        if idx.ndim != 4 or idx.shape[-1] != R:
+            raise ValueError(f"indices must be laid out (groups=1, batch, frames, residuals={R})")
+        codes = idx[0, :, :, 0] if R == 1 else idx[0]
         self._codec._check_codes(codes)
         return _cf(self._eng.vq_decode(codes))
 
@@ -338,12 +345,12 @@ class DistilCodec:
                 print(f"Encoded Mel spectrums: {tuple(_cf(feat).shape)}")
             codes, pin, fup, q = eng.vq_encode(feat, want_pjt_in=want, want_fup=want, want_quantized=want)
         zero = torch.zeros((), device=codes.device)
-        ret = GRVQResult(quantized=_cf(q) if q is not None else None, codes=codes.long()[None, :, :, None], codes_list=[],
+        ret = GRVQResult(quantized=_cf(q) if q is not None else None, codes=_gbtr(codes), codes_list=[],
                          total_loss=zero, commitment_loss=zero.clone(), codebook_diversity_loss=zero.clone(),
                          quantized_fup=fup, quantized_fup_list=[], x_pjt_in=pin, x_pjt_in_list=[])
         codes_host = codes.cpu()
         for b, hop_len in enumerate(n_hop_lengths):
-            codes_t = codes_host[b, :hop_len].tolist()
+            codes_t = codes_host[b, :hop_len].reshape(-1).tolist()  # frame-major: a frame's R codes together (:562)
             ret.codes_list.append(self.audio_tokenize(codes=codes_t, n_groups=self.ngroups, n_residual=self.nresiduals))
             if want:
                 ret.x_pjt_in_list.append(pin[b, :hop_len].reshape(hop_len * 2, -1).cpu())
@@ -351,7 +358,7 @@ class DistilCodec:
         return ret, gen_time_lengths, n_hop_lengths
 
     def _encode_ragged(self, audio_pathes: list, enable_bfloat16: bool, raw_audio: bool, codes_only: bool):
-        """`encode(..., ragged=True)`: `codes` is (1, B, T_max, 1) int64 with -1 (the reference's masked
+        """`encode(..., ragged=True)`: `codes` is (1, B, T_max, R) int64 with -1 (the reference's masked
         code, which `quantizer.decode` accepts) beyond each clip's own frames; `codes_list` and the
         `_list` features are trimmed per clip as in `encode`; `x_pjt_in` / `quantized_fup` are the
         packed (sum T, codebook_dim) tensors (None with `codes_only`); `quantized` is None."""
@@ -363,16 +370,16 @@ class DistilCodec:
         off = offsets.tolist()
         B = len(audio_list)
         t_max = max(off[b + 1] - off[b] for b in range(B))
-        padded = torch.full((B, t_max), -1, dtype=torch.int64, device=codes.device)
+        padded = torch.full((B, t_max) + tuple(codes.shape[1:]), -1, dtype=torch.int64, device=codes.device)
         for b in range(B):
             padded[b, : off[b + 1] - off[b]] = codes[off[b]: off[b + 1]]
         zero = torch.zeros((), device=codes.device)
-        ret = GRVQResult(quantized=None, codes=padded[None, :, :, None], codes_list=[], total_loss=zero,
+        ret = GRVQResult(quantized=None, codes=_gbtr(padded), codes_list=[], total_loss=zero,
                          commitment_loss=zero.clone(), codebook_diversity_loss=zero.clone(), quantized_fup=fup,
                          quantized_fup_list=[], x_pjt_in=pin, x_pjt_in_list=[])
         codes_host = codes.cpu()
         for b, hop_len in enumerate(n_hop_lengths):
-            codes_t = codes_host[off[b]: off[b] + hop_len].tolist()
+            codes_t = codes_host[off[b]: off[b] + hop_len].reshape(-1).tolist()
             ret.codes_list.append(self.audio_tokenize(codes=codes_t, n_groups=self.ngroups, n_residual=self.nresiduals))
             if want:
                 ret.x_pjt_in_list.append(pin[off[b]: off[b] + hop_len].reshape(hop_len * 2, -1).cpu())
@@ -384,19 +391,34 @@ class DistilCodec:
         if codes.numel() and (int(codes.max()) >= nc or int(codes.min()) < -nc):
             raise IndexError(f"audio code out of range for a codebook of {nc} entries")
 
+    def _frames(self, n_codes: int) -> int:
+        """Frames of a flat frame-major code list of `n_codes` entries (R per frame, as `encode`
+        yields them); ValueError for a length that is not a multiple of R."""
+        R = self.nresiduals
+        if n_codes % R:
+            raise ValueError(f"a code list of {n_codes} entries is not a multiple of the {R} codebooks per frame")
+        return n_codes // R
+
+    def _engine_codes(self, t: torch.Tensor) -> torch.Tensor:
+        """(B, T * R) flat frame-major codes -> the engine's (B, T) / (B, T, R)."""
+        R = self.nresiduals
+        return t if R == 1 else t.reshape(t.shape[0], self._frames(t.shape[1]), R)
+
     def decode_from_features(self, quantized_features: torch.Tensor, enable_bfloat16: bool = False) -> torch.Tensor:
         """distil_codec.py:575-579."""
         with self._precision(enable_bfloat16):
             return self.generator(quantized_features)
 
     def decode_from_codes(self, codes: list, minus_token_offset: bool = True, enable_bfloat16: bool = False) -> torch.Tensor:
-        """distil_codec.py:581-594 -> (1, 1, 256 n)."""
+        """distil_codec.py:581-594 -> (1, 1, 256 n).  With R > 1 codebooks `codes` is the flat
+        frame-major list `encode` yields (R entries per frame, n = len / R; ValueError otherwise); the
+        reference's own method is hard-wired to one code per frame."""
         if minus_token_offset:
             for c in codes:
                 if c - self.tokens_id_offset < 0:
                     print(f"c is :{c}", flush=True)
             codes = [c - self.tokens_id_offset for c in codes]
-        t = torch.tensor(codes, dtype=torch.int64)[None, :]
+        t = self._engine_codes(torch.tensor(codes, dtype=torch.int64)[None, :])
         self._check_codes(t)
         with torch.no_grad(), self._precision(enable_bfloat16) as eng:
             z = eng.vq_decode(t)
@@ -420,10 +442,13 @@ class DistilCodec:
             return []
         if minus_token_offset:
             codes_list = [[c - self.tokens_id_offset for c in codes] for codes in codes_list]
+        for c in codes_list:
+            self._frames(len(c))
         max_length = max(len(c) for c in codes_list)
         batched = torch.zeros(len(codes_list), max_length, dtype=torch.int64)
         for i, c in enumerate(codes_list):
             batched[i, : len(c)] = torch.tensor(c, dtype=torch.int64)
+        batched = self._engine_codes(batched)
         self._check_codes(batched)
         with self._precision(enable_bfloat16) as eng:
             wav = eng.generate(eng.vq_decode(batched))
@@ -435,7 +460,7 @@ class DistilCodec:
             raise ValueError("decode_from_codes_batch(ragged=True) runs in fp32 only: the bf16 kernels are not length-aware")
         if minus_token_offset:
             codes_list = [[c - self.tokens_id_offset for c in codes] for codes in codes_list]
-        codes, lengths = pad_code_lists(codes_list)
+        codes, lengths = pad_code_lists(codes_list, n_residual=self.nresiduals)
         check_codes_in_lengths(codes, lengths, self.quantizer_config.codebook_size)
         eng = self._engine()
         with torch.no_grad():
@@ -485,9 +510,7 @@ def decode_audio(codec: DistilCodec, audio_tsr, target_sr=24000, plus_offset: bo
     with torch.no_grad():
         audio = np.asarray(audio_tsr)[0]
         ret = codec.encode([[audio, target_sr]], enable_bfloat16=True, raw_audio=True, codes_only=True)[0]
-        codes = ret.codes.squeeze().cpu().tolist()
-        if isinstance(codes, int):
-            codes = [codes]
+        codes = ret.codes[0, 0].reshape(-1).cpu().tolist()  # frame-major, R codes per frame
         return [c + codec.tokens_id_offset for c in codes] if plus_offset else codes
 
 

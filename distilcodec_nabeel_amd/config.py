@@ -15,6 +15,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 DEFAULT_CONFIG_PATH = os.path.join(_HERE, "configs", "distilcodec_24k.json")
 
 
+MAX_CODEBOOKS = 8  # DCX_MAX_CODEBOOKS (include/distilcodec_amd.h)
+
+
 def load_config(path: str | None = None) -> dict:
     with open(path or DEFAULT_CONFIG_PATH) as f:
         return json.load(f)
@@ -27,8 +30,8 @@ def default_config() -> dict:
 def check_supported(cfg: dict) -> None:
     """Raise ValueError for architecture variants the native path does not implement.
 
-    The native path is specialised for the published DistilCodec geometry (single group,
-    single residual codebook, downsample factor 1, no template noise branch).  Anything else
+    The native path is specialised for the published DistilCodec geometry family (single group,
+    1 to 8 residual codebooks, downsample factor 1, no template noise branch).  Anything else
     is rejected loudly instead of silently computing something different.
     """
     q = cfg["quantizer"]
@@ -38,8 +41,10 @@ def check_supported(cfg: dict) -> None:
     problems = []
     if q.get("quantizer_type", "grvq") != "grvq":
         problems.append("quantizer_type must be 'grvq'")
-    if q["n_groups"] != 1 or q["n_codebooks"] != 1:
-        problems.append("only n_groups=1, n_codebooks=1 is supported")
+    if q["n_groups"] != 1:
+        problems.append("only n_groups=1 is supported")
+    if not isinstance(q["n_codebooks"], int) or not 1 <= q["n_codebooks"] <= MAX_CODEBOOKS:
+        problems.append(f"n_codebooks must be an integer in [1, {MAX_CODEBOOKS}]")
     if list(q["downsample_factor"]) != [1]:
         problems.append("only downsample_factor=[1] is supported")
     if d.get("use_template", False):

@@ -191,6 +191,17 @@ int dcx_finalize(dcx_codec* h, int32_t with_generator) {
   return DCX_OK;
 }
 
+int dcx_set_num_codebooks(dcx_codec* h, int32_t n) {
+  if (!h) return DCX_ERR_INVALID_ARG;
+  if (h->finalized) return fail(h, DCX_ERR_STATE, "dcx_set_num_codebooks after dcx_finalize");
+  if (n < 1 || n > DCX_MAX_CODEBOOKS)
+    return fail(h, DCX_ERR_INVALID_ARG, "n_codebooks must be in [1, " + std::to_string(DCX_MAX_CODEBOOKS) + "]");
+  h->n_layers = n;
+  return DCX_OK;
+}
+
+int32_t dcx_num_codebooks(const dcx_codec* h) { return h ? h->n_layers : 0; }
+
 int64_t dcx_num_frames(const dcx_codec* h, int64_t n) { return h ? frames_of(h->cfg, n) : 0; }
 
 size_t dcx_workspace_size(const dcx_codec* h, int32_t batch, int64_t frames) {

@@ -114,14 +114,23 @@ struct dcx_codec {
   ConvW vq_down, vq_pin, vq_up;
   BlockW vq_down_blk, vq_up_blk;
   int* rflag = nullptr;  // device RangeFlag bits (dcx_range_flags; round 6)
-  float *codebook = nullptr, *e2 = nullptr, *ptable = nullptr;
-  double* e2d = nullptr;          // |e|^2 per code in fp64 (the rescore)
-  float emax = 0.f, e2max = 0.f;  // largest codebook row norm / squared norm (prefilter bound)
-  float dmax = 0.f;               // largest |e - bf16(e)| over the codes (vq_prefilter_b1's bound)
+  // the residual chain (dcx_set_num_codebooks; residual_vq.py:140-259): layer k quantizes what layer
+  // k - 1 left over, each with its own codebook and search bounds; project_in / project_out are shared
+  int n_layers = 1;
+  struct VqLayer {
+    float *codebook = nullptr, *e2 = nullptr;
+    double* e2d = nullptr;          // |e|^2 per code in fp64 (the rescore)
+    float emax = 0.f, e2max = 0.f;  // largest codebook row norm / squared norm (prefilter bound)
+    float dmax = 0.f;               // largest |e - bf16(e)| over the codes (vq_prefilter_b1's bound)
+    unsigned short* codebook6 = nullptr;
+    unsigned short* codebook_b1 = nullptr;  // [CD/32][NC][32] bf16 hi (vq_prefilter_b1)
+  } vq[DCX_MAX_CODEBOOKS];
+  // project_out, live for the chain's decode (gather-sum, then this 1x1 conv: the reference's order) and
+  // the module hook; one codebook decodes through the tables below instead
+  ConvW vq_pout;
+  float* ptable = nullptr;
   int* vq_stats = nullptr;        // [rows rescored, codes rescored] (dcx_vq_rescore_stats)
   bool vq_stats_on = false;       // counted from the first dcx_vq_rescore_stats call on
-  unsigned short* codebook6 = nullptr;
-  unsigned short* codebook_b1 = nullptr;  // [CD/32][NC][32] bf16 hi (vq_prefilter_b1)
   unsigned short* ptable6 = nullptr;  // decode table as activation planes (x6 mode gathers)
   // bf16-mode decode table (planes; mid = lo = 0): project_out under autocast, bf16(bf16(E) W16^T + b16)
   unsigned short* ptable6b = nullptr;
@@ -430,8 +439,10 @@ int stage_encode(dcx_codec* h, CAct mel, int B, int T, Act feat, Bump& ws, hipSt
                  const dcx::RaggedSeg* rg = nullptr, bool fork = true);
 Layout vq_xlayout(const dcx_codec* h);
 VqScratch vq_scratch(const dcx_codec* h, Bump& ws, long long M, int ntiles, bool x6);
-int run_vq_search(dcx_codec* h, const float* P, const unsigned short* P6, Layout xl, long long M, const VqScratch& v,
-                  int ntiles, int32_t* codes, hipStream_t s);
+// layer: whose codebook; x_bf16: the rows of P are bf16 values (layer 0 in bf16 mode); have_norms: the
+// caller has filled v.x2 / x2d / xr2 and zeroed v.npairs (vq_residual_step), so row_sqnorm is skipped
+int run_vq_search(dcx_codec* h, int layer, const float* P, const unsigned short* P6, Layout xl, long long M,
+                  const VqScratch& v, int ntiles, int32_t* codes, hipStream_t s, bool x_bf16, bool have_norms = false);
 int stage_vq_encode(dcx_codec* h, CAct feat, int B, int T, int32_t* codes, float* pin, float* fup, float* quant,
                     Bump& ws, hipStream_t s, const dcx::RaggedSeg* rg = nullptr);
 // lens (ragged batches; device, [B]): codes at or beyond a clip's length are neither read nor counted,

@@ -447,6 +447,46 @@ hipError_t launch_split_planes(const float* x, unsigned short* y6, long long row
 hipError_t launch_gather_rows(const float* table, int ntable, const int32_t* idx, long long rows, int width,
                               float* out, int32_t* n_invalid, int masked_row, hipStream_t s,
                               const int* clip_len = nullptr, long long frames = 0);
+// ---- residual VQ (dcx_rvq.hip) ----
+constexpr int kMaxCodebooks = 8;  // DCX_MAX_CODEBOOKS
+// One layer's step of the chain on [rows][dim] fp32 rows (vq_residual_step): ck [rows] the layer's
+// codes, codes_out (optional) the [rows][R] codes tensor at this layer's column, fup (optional) = e
+// (fup_first) or += e, dst = src - e (null: the last layer; may be src) with its image op6 in
+// op_layout (planes / compact bf16) and the row quantities of launch_row_sqnorm (x2, x2d, xr2,
+// zero_me), each optional.
+struct VqResidualArgs {
+  const float* src;
+  const float* codebook;
+  const int32_t* ck;
+  int32_t* codes_out;
+  float* dst;
+  unsigned short* op6;
+  Layout op_layout;
+  float *x2, *xr2;
+  double* x2d;
+  unsigned long long* zero_me;
+  float* fup;
+  int fup_first;
+  long long rows;
+  int dim, ncodes, R;
+};
+hipError_t launch_vq_residual_step(const VqResidualArgs& a, hipStream_t s);
+// out[row] = sum over the R layers of table[k][idx[row][k]] in fp32, in layer order; an index -1 adds
+// nothing, the wrap / invalid-count / clip_len rules are launch_gather_rows'.  out (fp32) and / or out6
+// in out_layout (planes / compact bf16).
+struct GatherSumArgs {
+  const float* table[kMaxCodebooks];
+  const int32_t* idx;
+  float* out;
+  unsigned short* out6;
+  Layout out_layout;
+  int32_t* n_invalid;
+  const int* clip_len;
+  long long frames;
+  long long rows;
+  int dim, ncodes, R;
+};
+hipError_t launch_gather_sum_rows(const GatherSumArgs& a, hipStream_t s);
 // rows [r0, r1) of every clip of x [batch][L][C] set to zero, r0 = clip_len[b] * len_mul (ragged batches)
 hipError_t launch_zero_tail_rows(float* x, int batch, long long L, int C, const int* clip_len, int len_mul,
                                  hipStream_t s);

@@ -33,6 +33,7 @@ bool module_io(const dcx_codec* h, const std::string& m, int& cin, int& cout, in
       m == "quantizer.upsample.0.1")
     return set(c.vq_dim, c.vq_dim);
   if (m == "quantizer.grvq.rvqs.0.project_in") return set(c.vq_dim, c.codebook_dim);
+  if (m == "quantizer.grvq.rvqs.0.project_out") return set(c.codebook_dim, c.vq_dim);
   if (m == "quantizer.search") return set(c.codebook_dim, 0);
   if (m == "generator.conv_pre") return set(c.vq_dim, c.gen_channels);
   int ch = c.gen_channels;
@@ -125,6 +126,14 @@ int stage_module(dcx_codec* h, const std::string& m, const float* x, int B, int 
     cp.y = y;
     return run_conv(h, h->vq_pin, cp, s);
   }
+  if (m == "quantizer.grvq.rvqs.0.project_out") {  // residual_vq.py:138, 241
+    CAct in(x, nullptr);
+    RUN(ensure_planes(h, in, M, c.codebook_dim, ws, s, input_layout(h, h->vq_pout, M, false), 0));
+    WS_READY(h, ws, "workspace too small for the module");
+    ConvCall co = pointwise(in, M);
+    co.y = y;
+    return run_conv(h, h->vq_pout, co, s);
+  }
   // ConvNeXtBlock (convnext_utils.py:263-282)
   const BlockW* blk = nullptr;
   if (match_idx(m, "encoder.stages.%d.%d%n", &a, &b) && a >= 0 && a < 4 && b >= 0 && b < (int)h->blocks[a].size())
@@ -151,7 +160,7 @@ int stage_module(dcx_codec* h, const std::string& m, const float* x, int B, int 
   }
   // nearest-code search on x_pjt_in (EuclideanCodebook.forward, vector_quantize_pytorch.py:496-506)
   if (m == "quantizer.search") {
-    if (!h->codebook) return fail(h, DCX_ERR_STATE, "module weights not finalized");
+    if (!h->vq[0].codebook) return fail(h, DCX_ERR_STATE, "module weights not finalized");
     const int CD = c.codebook_dim, NC = c.codebook_size;
     // bf16 mode: the pipeline's search (compact bf16 x_pjt_in for the one-product prefilter, exact fp64
     // rescore of x as given).  The reference searches x.float() with autocast off
@@ -164,7 +173,7 @@ int stage_module(dcx_codec* h, const std::string& m, const float* x, int B, int 
     const VqScratch vs = vq_scratch(h, ws, M, ntiles, x6);
     WS_READY(h, ws, "workspace too small for the module");
     if (x6) LAUNCH(h, s, "split_planes", 0, 10.0 * M * CD, dcx::launch_split_planes(x, P6, M, CD, xl, s));
-    return run_vq_search(h, x, P6, xl, M, vs, ntiles, static_cast<int32_t*>(yv), s);
+    return run_vq_search(h, 0, x, P6, xl, M, vs, ntiles, static_cast<int32_t*>(yv), s, h->gemm_mode == DCX_GEMM_BF16);
   }
   if (!h->has_gen && m.rfind("generator.", 0) == 0) return fail(h, DCX_ERR_STATE, "generator weights were not finalized");
   if (m == "generator.conv_pre") {  // generators.py:121

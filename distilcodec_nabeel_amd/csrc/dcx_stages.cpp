@@ -192,7 +192,7 @@ int stage_encode(dcx_codec* h, CAct mel, int B, int T, Act feat, Bump& ws, hipSt
 
 // x_pjt_in layout the nearest-code search reads: compact bf16 for vq_prefilter_b1 (x6 and bf16
 // modes), else planes (vq_prefilter_dm / _x3; fp32 mode ignores it).
-Layout vq_xlayout(const dcx_codec* h) { return x6_mode(h) && h->compact && h->codebook_b1 ? LAYOUT_BF16 : LAYOUT_PLANES; }
+Layout vq_xlayout(const dcx_codec* h) { return x6_mode(h) && h->compact && h->vq[0].codebook_b1 ? LAYOUT_BF16 : LAYOUT_PLANES; }
 
 // The nearest-code search of DownsampleGRVQ (vector_quantize_pytorch.py:41-45, 496-506; first index on
 // ties) on x_pjt_in P (fp32 [M][CD]) and, in x6 / bf16 mode, P6 in the prefilter's layout xl (planes or
@@ -222,27 +222,30 @@ VqScratch vq_scratch(const dcx_codec* h, Bump& ws, long long M, int ntiles, bool
   return v;
 }
 
-int run_vq_search(dcx_codec* h, const float* P, const unsigned short* P6, Layout xl, long long M, const VqScratch& v,
-                  int ntiles, int32_t* codes, hipStream_t s) {
+int run_vq_search(dcx_codec* h, int layer, const float* P, const unsigned short* P6, Layout xl, long long M,
+                  const VqScratch& v, int ntiles, int32_t* codes, hipStream_t s, bool x_bf16, bool have_norms) {
   const dcx_config& c = h->cfg;
+  const dcx_codec::VqLayer& L = h->vq[layer];
   const int CD = c.codebook_dim, NC = c.codebook_size;
   const bool x6 = x6_mode(h);
   const bool b1 = xl == LAYOUT_BF16 && dcx::vq_b1_takes(NC, CD);
   float* const x2 = v.x2;
-  LAUNCH(h, s, "row_sqnorm", 2.0 * M * CD, 4.0 * M * CD,
-         dcx::launch_row_sqnorm(P, M, CD, x2, x6 ? v.x2d : nullptr, b1 ? v.xr2 : nullptr, x6 ? v.npairs : nullptr, s));
+  if (!have_norms)
+    LAUNCH(h, s, "row_sqnorm", 2.0 * M * CD, 4.0 * M * CD,
+           dcx::launch_row_sqnorm(P, M, CD, x2, x6 ? v.x2d : nullptr, b1 ? v.xr2 : nullptr, x6 ? v.npairs : nullptr, s));
   {
     ConvParams p{};
-    p.x = P; p.x6 = P6; p.w = h->codebook; p.w6 = x6 ? h->codebook6 : nullptr;
+    p.x = P; p.x6 = P6; p.w = L.codebook; p.w6 = x6 ? L.codebook6 : nullptr;
     p.Cin = CD; p.Cout = NC; p.ldx = CD; p.taps = 1; p.in_step = 1; p.out_mul = 1;
-    p.x2 = x2; p.e2 = h->e2; p.part_val = v.pv; p.part_idx = v.pi; p.part_val2 = v.pv2;
+    p.x2 = x2; p.e2 = L.e2; p.part_val = v.pv; p.part_idx = v.pi; p.part_val2 = v.pv2;
     p.x_layout = xl;
-    p.wc = b1 ? h->codebook_b1 : nullptr;
+    p.wc = b1 ? L.codebook_b1 : nullptr;
     ProfScope ps(h, s);
     const char* kname = "vq";
     if (x6) {
-      // bf16 mode rounds x_pjt_in to bf16 in the project_in epilogue (round_bf16)
-      HIPCHK(h, dcx::launch_vq_prefilter(p, (int)M, h->gemm_mode == DCX_GEMM_BF16, s, &kname));
+      // x_bf16: bf16 mode rounds x_pjt_in to bf16 in the project_in epilogue (round_bf16); a later
+      // layer's residual is not bf16-valued and takes the general form
+      HIPCHK(h, dcx::launch_vq_prefilter(p, (int)M, x_bf16, s, &kname));
       ps.done(kname, 2.0 * M * NC * CD, 4.0 * ((double)M * CD + (double)NC * CD));
     } else {
       HIPCHK(h, dcx::launch_vq_argmin(p, (int)M, s, &kname));
@@ -254,8 +257,8 @@ int run_vq_search(dcx_codec* h, const float* P, const unsigned short* P6, Layout
     a.part_val = v.pv; a.part_val2 = v.pv2; a.part_idx = v.pi;
     a.rows = M; a.ntiles = ntiles; a.tile_codes = NC / ntiles; a.dim = CD;
     a.x = P; a.x2 = x2; a.xr2 = b1 ? v.xr2 : nullptr; a.x2d = v.x2d;
-    a.codebook = h->codebook; a.e2d = h->e2d;
-    a.cx = dcx::vq_prefilter_cx(xl, NC, CD, h->emax, h->dmax); a.emax = h->emax; a.e2max = h->e2max;
+    a.codebook = L.codebook; a.e2d = L.e2d;
+    a.cx = dcx::vq_prefilter_cx(xl, NC, CD, L.emax, L.dmax); a.emax = L.emax; a.e2max = L.e2max;
     a.codes = codes; a.stats = h->vq_stats_on ? h->vq_stats : nullptr;
     a.pairs = v.pairs; a.cdist = v.cdist; a.ccode = v.ccode; a.cap = v.cap; a.row_list = v.row_list; a.npairs = v.npairs;
     LAUNCH(h, s, "vq_certify", 0, 12.0 * M * ntiles + 4.0 * M, dcx::launch_vq_certify(a, s));
@@ -275,9 +278,24 @@ static const unsigned short* decode_table6(const dcx_codec* h) {
 // The decode-table rows of M codes into zd (a conv_input: planes in x6 / bf16 mode, else fp32);
 // n_invalid: optional count of codes outside the codebook (they take the masked code's row)
 // lens / T (ragged batches): the rows are clips of T codes, those at or beyond lens[clip] are not read
-static int gather_decoded(dcx_codec* h, const int32_t* codes, long long M, Act zd, int32_t* n_invalid, hipStream_t s,
-                          const int* lens = nullptr, int T = 0) {
-  const int D = h->cfg.vq_dim, NC = h->cfg.codebook_size;
+// A chain (R > 1; codes [M][R]) decodes in the reference's order (residual_vq.py:103-138): the layers'
+// rows summed in fp32 into qs (project_out's input: fp32, or planes / compact bf16, whose hi plane is
+// bf16(sum) for the bf16 mode's autocast), then project_out as a 1x1 conv into zd in vq_up's layout.
+static int gather_decoded(dcx_codec* h, const int32_t* codes, long long M, Act zd, Act qs, int32_t* n_invalid,
+                          hipStream_t s, const int* lens = nullptr, int T = 0) {
+  const int D = h->cfg.vq_dim, NC = h->cfg.codebook_size, R = h->n_layers;
+  if (R > 1) {
+    const int CD = h->cfg.codebook_dim;
+    dcx::GatherSumArgs g{};
+    for (int k = 0; k < R; ++k) g.table[k] = h->vq[k].codebook;
+    g.idx = codes; g.out = qs.f; g.out6 = qs.p; g.out_layout = qs.lay; g.n_invalid = n_invalid;
+    g.clip_len = lens; g.frames = T; g.rows = M; g.dim = CD; g.ncodes = NC; g.R = R;
+    LAUNCH(h, s, "gather_sum_rows", 1.0 * M * CD * (R - 1), 4.0 * M * CD * R + (qs.p ? 2.0 * layout_u16(qs.lay) : 4.0) * M * CD,
+           dcx::launch_gather_sum_rows(g, s));
+    ConvCall co = pointwise(qs, M);
+    co.out_to(zd);
+    return run_conv(h, h->vq_pout, co, s);
+  }
   if (x6_mode(h))
     LAUNCH(h, s, "gather_rows", 0, 12.0 * M * D,
            dcx::launch_gather_rows((const float*)decode_table6(h), NC, codes, M, D * 3 / 2, (float*)zd.p, n_invalid, NC, s,
@@ -286,6 +304,21 @@ static int gather_decoded(dcx_codec* h, const int32_t* codes, long long M, Act z
     LAUNCH(h, s, "gather_rows", 0, 8.0 * M * D,
            dcx::launch_gather_rows(h->ptable, NC, codes, M, D, zd.f, n_invalid, NC, s, lens, T));
   return DCX_OK;
+}
+
+// project_out's input of a chain's decode: M rows of codebook_dim in the layout the conv reads in this
+// mode (fp32; compact bf16 where conv_gemm_bf16dm takes it; else planes).  Nothing for one codebook.
+static Act alloc_qsum(dcx_codec* h, Bump& ws, long long M) {
+  Act qs;
+  if (h->n_layers < 2) return qs;
+  const size_t n = (size_t)M * h->cfg.codebook_dim;
+  if (!x6_mode(h)) {
+    qs.f = ws.f(n);
+    return qs;
+  }
+  qs.lay = takes_compact(h, h->vq_pout, M) ? LAYOUT_BF16 : LAYOUT_PLANES;
+  qs.p = ws.u16(n * 3);  // planes-sized in either layout, as conv_input: the size does not follow the mode's kernels
+  return qs;
 }
 
 int stage_vq_encode(dcx_codec* h, CAct feat, int B, int T, int32_t* codes, float* pin, float* fup, float* quant,
@@ -311,6 +344,12 @@ int stage_vq_encode(dcx_codec* h, CAct feat, int B, int T, int32_t* codes, float
   unsigned short* P6 = x6 ? ws.u16((size_t)M * CD * 3) : nullptr;
   const VqScratch vs = vq_scratch(h, ws, M, ntiles, x6);
   Act zd = conv_input(h, ws, (size_t)M * D);
+  // a chain: the fp32 residual (x_pjt_in itself is kept: the caller may have asked for it), one layer's
+  // codes as the search writes them, and project_out's input
+  const int R = h->n_layers;
+  float* Rs = R > 1 ? ws.f((size_t)M * CD) : nullptr;
+  int32_t* ck = R > 1 ? ws.i((size_t)M) : nullptr;
+  Act qs = alloc_qsum(h, ws, M);
   WS_READY(h, ws, "workspace too small for vq_encode");
   ConvCall cd = pointwise(feat, M);
   cd.y = X;
@@ -328,10 +367,29 @@ int stage_vq_encode(dcx_codec* h, CAct feat, int B, int T, int32_t* codes, float
   cp.y6 = P6;
   cp.y_lay = xl;
   RUN(run_conv(h, h->vq_pin, cp, s));
-  RUN(run_vq_search(h, P, P6, xl, M, vs, ntiles, codes, s));
-  if (fup) LAUNCH(h, s, "gather_rows", 0, 8.0 * M * CD, dcx::launch_gather_rows(h->codebook, NC, codes, M, CD, fup, nullptr, -1, s));
+  const bool bf16 = h->gemm_mode == DCX_GEMM_BF16;
+  if (R == 1) {
+    RUN(run_vq_search(h, 0, P, P6, xl, M, vs, ntiles, codes, s, bf16));
+    if (fup) LAUNCH(h, s, "gather_rows", 0, 8.0 * M * CD, dcx::launch_gather_rows(h->vq[0].codebook, NC, codes, M, CD, fup, nullptr, -1, s));
+  }
+  // the chain (residual_vq.py:208-259): layer k searches r_k, then one pass writes its codes into
+  // column k, adds its rows to fup and leaves r_{k+1} = fl32(r_k - E_k[c_k]) with everything the next
+  // search reads (its operand image, its row norms, the zeroed pair counter)
+  for (int k = 0; R > 1 && k < R; ++k) {
+    RUN(run_vq_search(h, k, k ? Rs : P, P6, xl, M, vs, ntiles, ck, s, bf16 && k == 0, /*have_norms=*/k > 0));
+    const bool last = k == R - 1;
+    const bool b1 = xl == LAYOUT_BF16 && dcx::vq_b1_takes(NC, CD);
+    dcx::VqResidualArgs a{};
+    a.src = k ? Rs : P; a.codebook = h->vq[k].codebook; a.ck = ck; a.codes_out = codes + k;
+    a.dst = last ? nullptr : Rs; a.op6 = last ? nullptr : P6; a.op_layout = xl;
+    a.x2 = last ? nullptr : vs.x2; a.x2d = last || !x6 ? nullptr : vs.x2d; a.xr2 = last || !b1 ? nullptr : vs.xr2;
+    a.zero_me = last || !x6 ? nullptr : vs.npairs;
+    a.fup = fup; a.fup_first = k == 0; a.rows = M; a.dim = CD; a.ncodes = NC; a.R = R;
+    const double rw = (last ? 0.0 : 8.0 + (P6 ? 2.0 * layout_u16(xl) : 0.0)) + (fup ? (k ? 8.0 : 4.0) : 0.0);
+    LAUNCH(h, s, "vq_residual_step", last ? 0.0 : 3.0 * M * CD, (4.0 + rw) * M * CD, dcx::launch_vq_residual_step(a, s));
+  }
   if (quant) {
-    RUN(gather_decoded(h, codes, M, zd, nullptr, s));
+    RUN(gather_decoded(h, codes, M, zd, qs, nullptr, s));
     ConvCall cu = pointwise(zd, M);
     cu.y = quant;
     RUN(run_conv(h, h->vq_up, cu, s));
@@ -350,9 +408,10 @@ int stage_vq_decode(dcx_codec* h, const int32_t* codes, int B, int T, Act z, int
   Act ln = conv_input(h, ws, (size_t)M * D);
   Act hid = conv_input(h, ws, (size_t)M * 4 * D);
   row_ranges(h, ws, M, ln, hid);
+  Act qs = alloc_qsum(h, ws, M);
   WS_READY(h, ws, "workspace too small for vq_decode");
   if (z.p && z.lay == LAYOUT_H2) return fail(h, DCX_ERR_STATE, "internal: z in h2 is split by the generator (ranged per clip)");
-  RUN(gather_decoded(h, codes, M, zd, n_invalid, s, lens, T));
+  RUN(gather_decoded(h, codes, M, zd, qs, n_invalid, s, lens, T));
   ConvCall cu = pointwise(zd, M);
   cu.y = z.f;
   RUN(run_conv(h, h->vq_up, cu, s));
@@ -500,7 +559,7 @@ int stage_encode_decode(dcx_codec* h, const float* audio, int B, int64_t n, int3
   auto half = [&](int b0, int nb, Bump& w, hipStream_t st) -> int {
     const bool dry = w.dry;
     const float* a = dry ? nullptr : audio + (long long)b0 * n;
-    int32_t* cd = dry ? nullptr : codes + (long long)b0 * T;
+    int32_t* cd = dry ? nullptr : codes + (long long)b0 * T * h->n_layers;
     // inside a half the encoder does not fork again
     if (mode == 2)
       return encode_clips_to_z(h, a, nb, n, cd, act_rows_out(z, b0, (long long)b0 * T, h->cfg.vq_dim), w, st, /*fork=*/false);

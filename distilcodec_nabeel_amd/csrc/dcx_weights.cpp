@@ -377,9 +377,15 @@ static int build_all(dcx_codec* h, Builder& B, int32_t with_generator) {
     h->vq_up = B.convT(q + "upsample.0.0", D, D, 1, 1);
     h->vq_up_blk = B.block(q + "upsample.0.1", D);
     h->vq_pin = B.conv(q + "grvq.rvqs.0.project_in", D, CD, 1, 1, 0, true, true);  // + h3 weights
-    ConvW pout = B.conv(q + "grvq.rvqs.0.project_out", CD, D, 1, 1, 0);
-    auto emb = B.need(q + "grvq.rvqs.0.layers.0._codebook.embed", {1, NC, CD});
-    if (emb) {
+    h->vq_pout = B.conv(q + "grvq.rvqs.0.project_out", CD, D, 1, 1, 0);
+    const ConvW& pout = h->vq_pout;
+    const int R = h->n_layers;
+    h->vq_stats = (int*)B.upload(std::vector<float>(2, 0.f));  // zero counters
+    // every layer of the chain: a missing codebook fails the load (never a shorter chain)
+    for (int k = 0; k < R; ++k) {
+      auto emb = B.need(q + "grvq.rvqs.0.layers." + std::to_string(k) + "._codebook.embed", {1, NC, CD});
+      if (!emb) break;
+      dcx_codec::VqLayer& L = h->vq[k];
       std::vector<float> e2(NC);
       std::vector<double> e2d(NC);
       double e2m = 0;
@@ -390,14 +396,13 @@ static int build_all(dcx_codec* h, Builder& B, int32_t with_generator) {
         e2d[i] = sacc;
         e2m = std::max(e2m, sacc);
       }
-      h->e2d = (double*)B.upload_raw(e2d.data(), e2d.size() * sizeof(double));
+      L.e2d = (double*)B.upload_raw(e2d.data(), e2d.size() * sizeof(double));
       // rounded up so the prefilter bound stays an upper bound
-      h->e2max = std::nextafter((float)e2m, INFINITY);
-      h->emax = std::nextafter((float)std::sqrt(e2m), INFINITY);
-      h->vq_stats = (int*)B.upload(std::vector<float>(2, 0.f));  // zero counters
-      h->codebook = B.upload(emb->data);
-      h->codebook6 = B.split_pack(emb->data, 1, NC, 1, CD);
-      h->e2 = B.upload(e2);
+      L.e2max = std::nextafter((float)e2m, INFINITY);
+      L.emax = std::nextafter((float)std::sqrt(e2m), INFINITY);
+      L.codebook = B.upload(emb->data);
+      L.codebook6 = B.split_pack(emb->data, 1, NC, 1, CD);
+      L.e2 = B.upload(e2);
       // max |e - bf16(e)| in fp64, rounded up (vq_prefilter_b1's bound)
       double d2m = 0;
       for (int i = 0; i < NC; ++i) {
@@ -409,53 +414,58 @@ static int build_all(dcx_codec* h, Builder& B, int32_t with_generator) {
         }
         d2m = std::max(d2m, sacc);
       }
-      h->dmax = std::nextafter((float)(std::sqrt(d2m) * (1.0 + 1e-12)), INFINITY);
-      if (dcx::vq_b1_takes(NC, CD)) h->codebook_b1 = B.compact_pack(emb->data, NC, CD);
+      L.dmax = std::nextafter((float)(std::sqrt(d2m) * (1.0 + 1e-12)), INFINITY);
+      if (dcx::vq_b1_takes(NC, CD)) L.codebook_b1 = B.compact_pack(emb->data, NC, CD);
     }
-    // decode table: project_out applied to every code once, E * W_out^T + b_out.  Row NC holds
-    // project_out(0) = b_out, the row of the reference's masked code -1 (residual_vq.py:120-127:
-    // masked_fill(-1 -> 0), gather, then the gathered vector zeroed before project_out).
-    h->ptable = B.alloc((size_t)(NC + 1) * D);
-    h->ptable6 = (unsigned short*)B.alloc((size_t)(NC + 1) * D * 3 / 2);
-    if (!B.bad() && !B.dry) {
-      // built once with the fp32 MFMA path (the codebook is not held as activation planes)
-      ConvCall cp = pointwise(CAct(h->codebook, nullptr), NC);
-      cp.y = h->ptable;
-      int rc = run_conv(h, pout, cp, 0, /*force_f32=*/true);
-      if (rc != DCX_OK) return rc;
-      if (hipMemcpy(h->ptable + (size_t)NC * D, pout.b, sizeof(float) * D, hipMemcpyDeviceToDevice) != hipSuccess ||
-          dcx::launch_split_planes(h->ptable, h->ptable6, NC + 1, D, LAYOUT_PLANES, 0) != hipSuccess ||
-          hipDeviceSynchronize() != hipSuccess)
-        return fail(h, DCX_ERR_HIP, "decode-table build failed");
-    }
-    // The bf16 mode's table: project_out under the reference's autocast (residual_vq.py:138 inside
-    // distil_codec.py:590), bf16(bf16(E) W_out16^T + b_out16) by the one-product conv on the codebook
-    // as activation planes (scratch); row NC = bf16(b_out) (the masked code).  Built in a scratch fp32
-    // table, then split.
-    h->ptable6b = (unsigned short*)B.alloc((size_t)(NC + 1) * D * 3 / 2);
-    if (!B.bad() && !B.dry && h->codebook) {
-      float* tmp = nullptr;
-      unsigned short* e6 = nullptr;
-      if (hipMalloc(&tmp, sizeof(float) * (size_t)(NC + 1) * D) != hipSuccess) return fail(h, DCX_ERR_OOM, "hipMalloc failed");
-      if (hipMalloc(&e6, sizeof(unsigned short) * 3 * (size_t)NC * CD) != hipSuccess) {
-        hipFree(tmp);
-        return fail(h, DCX_ERR_OOM, "hipMalloc failed");
+    float* const codebook = h->vq[0].codebook;
+    // A chain decodes by gather-sum and the project_out conv (stage_vq_decode), in the reference's
+    // order; only one codebook has a table of its project_out rows.
+    if (R == 1) {
+      // decode table: project_out applied to every code once, E * W_out^T + b_out.  Row NC holds
+      // project_out(0) = b_out, the row of the reference's masked code -1 (residual_vq.py:120-127:
+      // masked_fill(-1 -> 0), gather, then the gathered vector zeroed before project_out).
+      h->ptable = B.alloc((size_t)(NC + 1) * D);
+      h->ptable6 = (unsigned short*)B.alloc((size_t)(NC + 1) * D * 3 / 2);
+      if (!B.bad() && !B.dry) {
+        // built once with the fp32 MFMA path (the codebook is not held as activation planes)
+        ConvCall cp = pointwise(CAct(codebook, nullptr), NC);
+        cp.y = h->ptable;
+        int rc = run_conv(h, pout, cp, 0, /*force_f32=*/true);
+        if (rc != DCX_OK) return rc;
+        if (hipMemcpy(h->ptable + (size_t)NC * D, pout.b, sizeof(float) * D, hipMemcpyDeviceToDevice) != hipSuccess ||
+            dcx::launch_split_planes(h->ptable, h->ptable6, NC + 1, D, LAYOUT_PLANES, 0) != hipSuccess ||
+            hipDeviceSynchronize() != hipSuccess)
+          return fail(h, DCX_ERR_HIP, "decode-table build failed");
       }
-      int rc = dcx::launch_split_planes(h->codebook, e6, NC, CD, LAYOUT_PLANES, 0) == hipSuccess
-                   ? DCX_OK : fail(h, DCX_ERR_HIP, "codebook split failed");
-      const int mode = h->gemm_mode;
-      h->gemm_mode = DCX_GEMM_BF16;
-      ConvCall cp = pointwise(CAct(h->codebook, e6), NC);
-      cp.y = tmp;
-      if (rc == DCX_OK) rc = run_conv(h, pout, cp, 0);
-      h->gemm_mode = mode;
-      if (rc == DCX_OK &&
-          (hipMemcpy(tmp + (size_t)NC * D, pout.b16, sizeof(float) * D, hipMemcpyDeviceToDevice) != hipSuccess ||
-           dcx::launch_split_planes(tmp, h->ptable6b, NC + 1, D, LAYOUT_PLANES, 0) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
-        rc = fail(h, DCX_ERR_HIP, "bf16 decode-table build failed");
-      hipFree(e6);
-      hipFree(tmp);
-      if (rc != DCX_OK) return rc;
+      // The bf16 mode's table: project_out under the reference's autocast (residual_vq.py:138 inside
+      // distil_codec.py:590), bf16(bf16(E) W_out16^T + b_out16) by the one-product conv on the codebook
+      // as activation planes (scratch); row NC = bf16(b_out) (the masked code).  Built in a scratch fp32
+      // table, then split.
+      h->ptable6b = (unsigned short*)B.alloc((size_t)(NC + 1) * D * 3 / 2);
+      if (!B.bad() && !B.dry && codebook) {
+        float* tmp = nullptr;
+        unsigned short* e6 = nullptr;
+        if (hipMalloc(&tmp, sizeof(float) * (size_t)(NC + 1) * D) != hipSuccess) return fail(h, DCX_ERR_OOM, "hipMalloc failed");
+        if (hipMalloc(&e6, sizeof(unsigned short) * 3 * (size_t)NC * CD) != hipSuccess) {
+          hipFree(tmp);
+          return fail(h, DCX_ERR_OOM, "hipMalloc failed");
+        }
+        int rc = dcx::launch_split_planes(codebook, e6, NC, CD, LAYOUT_PLANES, 0) == hipSuccess
+                     ? DCX_OK : fail(h, DCX_ERR_HIP, "codebook split failed");
+        const int mode = h->gemm_mode;
+        h->gemm_mode = DCX_GEMM_BF16;
+        ConvCall cp = pointwise(CAct(codebook, e6), NC);
+        cp.y = tmp;
+        if (rc == DCX_OK) rc = run_conv(h, pout, cp, 0);
+        h->gemm_mode = mode;
+        if (rc == DCX_OK &&
+            (hipMemcpy(tmp + (size_t)NC * D, pout.b16, sizeof(float) * D, hipMemcpyDeviceToDevice) != hipSuccess ||
+             dcx::launch_split_planes(tmp, h->ptable6b, NC + 1, D, LAYOUT_PLANES, 0) != hipSuccess || hipDeviceSynchronize() != hipSuccess))
+          rc = fail(h, DCX_ERR_HIP, "bf16 decode-table build failed");
+        hipFree(e6);
+        hipFree(tmp);
+        if (rc != DCX_OK) return rc;
+      }
     }
     // the h3 range flags (round 6)
     if (!B.bad() && !B.dry) {

@@ -62,6 +62,9 @@ class NativeCodec:
             if self.gemm not in GEMM_MODES:
                 raise ValueError(f"unknown GEMM mode {self.gemm!r}; expected one of {sorted(GEMM_MODES)}")
             self._check(self.L.dcx_set_gemm_mode(self.h, GEMM_MODES[self.gemm]))
+            # residual codebooks (ResidualVQ): codes carry an innermost axis of R entries when R > 1
+            self._check(self.L.dcx_set_num_codebooks(self.h, int(cfg["quantizer"]["n_codebooks"])))
+            self.R = int(self.L.dcx_num_codebooks(self.h))
             for part in ("encoder", "quantizer") + (("generator",) if with_generator else ()):
                 for k, v in state[part].items():
                     if k.endswith(_TRAINING_ONLY):
@@ -117,6 +120,18 @@ class NativeCodec:
             self._ws = None
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
+
+    def _codes_shape(self, *lead) -> tuple:
+        """Shape of a codes tensor: `lead` alone for one codebook, `lead + (R,)` for a chain."""
+        return tuple(lead) if self.R == 1 else tuple(lead) + (self.R,)
+
+    def _codes_in(self, codes) -> torch.Tensor:
+        """A caller's codes as int32 on the device, [B, T] (R == 1) or [B, T, R]."""
+        codes = self._dev(codes, torch.int32)
+        want = 2 if self.R == 1 else 3
+        if codes.ndim != want or (self.R > 1 and codes.shape[2] != self.R):
+            raise ValueError(f"codes must be shaped {self._codes_shape('B', 'T')}, got {tuple(codes.shape)}")
+        return codes
 
     @staticmethod
     def _ptr(t):
@@ -205,7 +220,7 @@ class NativeCodec:
                   ws: torch.Tensor | None = None):
         feat = self._dev(feat, torch.float32)
         B, T, _ = feat.shape
-        codes = torch.empty(B, T, dtype=torch.int32, device=self.device)
+        codes = torch.empty(self._codes_shape(B, T), dtype=torch.int32, device=self.device)
         pin = torch.empty(B, T, self.CD, device=self.device) if want_pjt_in else None
         fup = torch.empty(B, T, self.CD, device=self.device) if want_fup else None
         q = torch.empty(B, T, self.D, device=self.device) if want_quantized else None
@@ -216,8 +231,8 @@ class NativeCodec:
         return codes, pin, fup, q
 
     def vq_decode(self, codes: torch.Tensor, ws: torch.Tensor | None = None) -> torch.Tensor:
-        codes = self._dev(codes, torch.int32)
-        B, T = codes.shape
+        codes = self._codes_in(codes)
+        B, T = codes.shape[:2]
         z = torch.empty(B, T, self.D, device=self.device)
         ws = self.workspace(B, T, ws)
         with torch.cuda.device(self.device):
@@ -242,7 +257,9 @@ class NativeCodec:
         B, N = audio.shape
         T = self.num_frames(N)
         if codes is None:
-            codes = torch.empty(B, T, dtype=torch.int32, device=self.device)
+            codes = torch.empty(self._codes_shape(B, T), dtype=torch.int32, device=self.device)
+        elif self.R > 1 and (tuple(codes.shape) != self._codes_shape(B, T) or codes.dtype != torch.int32 or not codes.is_contiguous()):
+            raise ValueError(f"codes must be a contiguous int32 tensor shaped {self._codes_shape(B, T)}")
         if wav is None:
             wav = torch.empty(B, self.hop * T, device=self.device)
         ws = self.workspace(B, T, ws)
@@ -265,7 +282,7 @@ class NativeCodec:
 
     def tokenize_ragged(self, clips, want_pjt_in: bool = False, want_fup: bool = False, ws: torch.Tensor | None = None):
         """Clips of different lengths (1-D tensors or arrays of raw samples, without the reference's
-        leading zero) -> (codes int32 [sum T], frame_offsets int64 [B + 1] (host), x_pjt_in | None,
+        leading zero) -> (codes int32 [sum T] ([sum T, R] for R > 1 codebooks), frame_offsets int64 [B + 1] (host), x_pjt_in | None,
         quantized_fup | None), the last two packed [sum T, codebook_dim].  The clips are packed back to
         back and tokenized in one call with no padding (dcx_tokenize_ragged); clip b's rows are
         [frame_offsets[b], frame_offsets[b + 1]) and equal what the clip gives alone."""
@@ -279,7 +296,7 @@ class NativeCodec:
         plan_dev = torch.from_numpy(plan).to(self.device)
         offsets = torch.tensor(np.concatenate([[0], np.cumsum([self.num_frames(n + 1) for n in lengths])]), dtype=torch.int64)
         assert int(offsets[-1]) == total_frames
-        codes = torch.empty(total_frames, dtype=torch.int32, device=self.device)
+        codes = torch.empty(self._codes_shape(total_frames), dtype=torch.int32, device=self.device)
         pin = torch.empty(total_frames, self.CD, device=self.device) if want_pjt_in else None
         fup = torch.empty(total_frames, self.CD, device=self.device) if want_fup else None
         ws = self._workspace_of(int(self.L.dcx_ragged_workspace_size(self.h, B, total_frames)), ws)
@@ -321,14 +338,14 @@ class NativeCodec:
 
     def decode_ragged(self, codes: torch.Tensor, lengths, ws: torch.Tensor | None = None,
                       wav: torch.Tensor | None = None, n_invalid: torch.Tensor | None = None) -> torch.Tensor:
-        """codes (B, T_max) int32 with per-clip frame counts `lengths` -> wav (B, 256 T_max), as
+        """codes (B, T_max) int32 ((B, T_max, R) for R > 1 codebooks) with per-clip frame counts `lengths` -> wav (B, 256 T_max), as
         generate_ragged (dcx_decode_ragged).  Entries at or beyond a length are never read;
         n_invalid (device int32 [1], optional, zeroed by the caller) counts codes outside the
         codebook below the lengths."""
         if not self.with_generator:
             raise RuntimeError("this engine was built without generator weights")
-        codes = self._dev(codes, torch.int32)
-        B, T = codes.shape
+        codes = self._codes_in(codes)
+        B, T = codes.shape[:2]
         lens = self._ragged_lengths(lengths, B, T)
         if wav is None:
             wav = torch.empty(B, self.hop * T, device=self.device)
@@ -357,7 +374,7 @@ class NativeCodec:
         need = int(self.L.dcx_module_workspace_size(self.h, n, B, L))
         if need == 0:
             raise ValueError(f"module {name!r} cannot run on this handle")
-        if cout == 0:
+        if cout == 0:  # "quantizer.search": layer 0's codes, one per row
             y = torch.empty(B, L, dtype=torch.int32, device=self.device)
         else:
             y = torch.empty(B, L * rate, cout, device=self.device)

@@ -30,18 +30,29 @@ def check_lengths(lengths, batch: int, frames_max: int) -> np.ndarray:
     return np.ascontiguousarray(a64.astype(np.int32))
 
 
-def pad_code_lists(codes_list, pad: int = PAD_CODE) -> tuple[np.ndarray, np.ndarray]:
+def pad_code_lists(codes_list, pad: int = PAD_CODE, n_residual: int = 1) -> tuple[np.ndarray, np.ndarray]:
     """Code lists of different lengths -> (codes int32 [B, T_max] filled with `pad` beyond each
     list, lengths int32 [B]).  T_max is at least 1, so a batch of empty lists is still a valid
-    (all-zero output) call.  ValueError for an empty batch or a code that does not fit int32."""
+    (all-zero output) call.  ValueError for an empty batch or a code that does not fit int32.
+    `n_residual` = R > 1: the lists are flat and frame-major, R codes per frame (as `encode` yields
+    them); codes is [B, T_max, R], lengths count frames, and a list whose length is not a multiple
+    of R is a ValueError."""
     if len(codes_list) == 0:
         raise ValueError("ragged decode needs at least one clip")
+    R = int(n_residual)
+    if R < 1:
+        raise ValueError("n_residual must be >= 1")
     rows = [np.asarray(c, dtype=np.int64).reshape(-1) for c in codes_list]
-    lengths = np.array([r.shape[0] for r in rows], dtype=np.int32)
+    for b, r in enumerate(rows):
+        if r.shape[0] % R:
+            raise ValueError(f"clip {b}: a code list of {r.shape[0]} entries is not a multiple of the {R} codebooks per frame")
+    lengths = np.array([r.shape[0] // R for r in rows], dtype=np.int32)
     t_max = max(1, int(lengths.max()))
-    out = np.full((len(rows), t_max), pad, dtype=np.int64)
+    out = np.full((len(rows), t_max * R), pad, dtype=np.int64)
     for b, r in enumerate(rows):
         out[b, : r.shape[0]] = r
+    if R > 1:
+        out = out.reshape(len(rows), t_max, R)
     if out.min() < np.iinfo(np.int32).min or out.max() > np.iinfo(np.int32).max:
         raise ValueError("audio code does not fit 32 bits")
     return np.ascontiguousarray(out.astype(np.int32)), check_lengths(lengths, len(rows), t_max)
@@ -49,11 +60,15 @@ def pad_code_lists(codes_list, pad: int = PAD_CODE) -> tuple[np.ndarray, np.ndar
 
 def check_codes_in_lengths(codes: np.ndarray, lengths: np.ndarray, codebook_size: int) -> None:
     """IndexError, like torch indexing, for a code outside [-codebook_size, codebook_size) among a
-    clip's own entries; what lies beyond a clip's length is not looked at."""
+    clip's own entries; what lies beyond a clip's length is not looked at.  codes: [B, T] or, for R
+    codebooks per frame, [B, T, R] (every layer's entry is checked)."""
     t = np.arange(codes.shape[1])[None, :]
     live = t < np.asarray(lengths)[:, None]
+    if codes.ndim == 3:
+        live = live[:, :, None]
     bad = live & ((codes >= codebook_size) | (codes < -codebook_size))
     if bad.any():
-        b, i = (int(v[0]) for v in np.nonzero(bad))
-        raise IndexError(f"audio code {int(codes[b, i])} (clip {b}, frame {i}) out of range for a codebook of "
+        at = tuple(int(v[0]) for v in np.nonzero(bad))
+        where = f"clip {at[0]}, frame {at[1]}" + (f", layer {at[2]}" if codes.ndim == 3 else "")
+        raise IndexError(f"audio code {int(codes[at])} ({where}) out of range for a codebook of "
                          f"{codebook_size} entries")

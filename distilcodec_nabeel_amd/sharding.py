@@ -83,7 +83,7 @@ class ShardedEncodeDecode:
         self.audio = torch.from_numpy(pad_to_global(local_clips, global_max)).to(engine.device)
         T = engine.num_frames(global_max + 1)
         self.frames = T
-        self.codes = torch.empty(len(local_clips), T, dtype=torch.int32, device=engine.device)
+        self.codes = torch.empty(engine._codes_shape(len(local_clips), T), dtype=torch.int32, device=engine.device)
         self.wav = torch.empty(len(local_clips), engine.hop * T, device=engine.device)
 
     def step(self, gather: bool = True):

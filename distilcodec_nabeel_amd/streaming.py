@@ -34,7 +34,7 @@ class GraphedHop:
         self.batch = batch
         self.frames = engine.num_frames(hop_samples + 1)
         self.audio = torch.zeros(batch, hop_samples + 1, device=self.device)  # [:, 0] stays 0
-        self.codes = torch.empty(batch, self.frames, dtype=torch.int32, device=self.device)
+        self.codes = torch.empty(engine._codes_shape(batch, self.frames), dtype=torch.int32, device=self.device)
         self.wav = torch.empty(batch, engine.hop * self.frames, device=self.device)
         # The graph records raw pointers, so it owns its workspace: the engine's shared buffer is
         # reallocated whenever a later call on the same engine needs more (a longer clip, a
@@ -122,7 +122,7 @@ class HaloStream:
         # from frame c_off
         self.audio = torch.zeros(1, device=engine.device)
         self.a_off = 0
-        self.codes = torch.empty(0, dtype=torch.int32, device=engine.device)
+        self.codes = torch.empty(engine._codes_shape(0), dtype=torch.int32, device=engine.device)  # [frames(, R)]
         self.c_off = 0
         self.emitted = 0  # frames whose audio was returned
         self.done = False
@@ -145,7 +145,7 @@ class HaloStream:
         self.t_gen = -(-push // hop) + 1 + 2 * self.gen_halo
         dev = eng.device
         self.a_win = torch.zeros(1, self.n_enc, device=dev)
-        self.c_win = torch.zeros(1, self.t_gen, dtype=torch.int32, device=dev)
+        self.c_win = torch.zeros(eng._codes_shape(1, self.t_gen), dtype=torch.int32, device=dev)
         t_enc = eng.num_frames(self.n_enc)
         self.ws = torch.empty(max(eng.workspace_size(1, t_enc), eng.workspace_size(1, self.t_gen)),
                               dtype=torch.uint8, device=dev)
@@ -194,7 +194,7 @@ class HaloStream:
         eng = self.engine
         if self.push_samples is None or final:
             return eng.generate(eng.vq_decode(codes.unsqueeze(0)))[0]
-        n = codes.numel()
+        n = codes.shape[0]
         if n > self.t_gen:
             raise ValueError(f"push larger than the fixed window allows (push_samples={self.push_samples})")
         self.c_win[0, :n].copy_(codes)
@@ -207,7 +207,7 @@ class HaloStream:
     # ------------------------------------------------------------------ stream
     @property
     def n_codes(self) -> int:
-        return self.c_off + self.codes.numel()
+        return self.c_off + self.codes.shape[0]
 
     def _final_codes(self, final: bool) -> int:
         n = self.a_off + self.audio.numel()

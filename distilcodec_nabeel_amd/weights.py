@@ -127,6 +127,11 @@ def synthetic_quantizer(cfg: dict, seed: int = 1234) -> dict:
     qd["grvq.rvqs.0.project_out.bias"] = _normal(seed, "q.pout.b", (D,), 0.05)
     qd["grvq.rvqs.0.layers.0._codebook.embed"] = _normal(seed, "q.codebook", (1, NC, CD), CODEBOOK_STD)
     qd["grvq.rvqs.0.layers.0._codebook.initted"] = np.ones((1,), np.float32)
+    # residual layers (n_codebooks > 1) under keys of their own, so layer 0 and every other tensor
+    # keep the values of the one-codebook state; every layer draws at the codebook's std
+    for k in range(1, int(q_cfg.get("n_codebooks", 1))):
+        qd[f"grvq.rvqs.0.layers.{k}._codebook.embed"] = _normal(seed, f"q.codebook.{k}", (1, NC, CD), CODEBOOK_STD)
+        qd[f"grvq.rvqs.0.layers.{k}._codebook.initted"] = np.ones((1,), np.float32)
     return qd
 
 

@@ -27,6 +27,7 @@ extern "C" {
 #endif
 
 #define DCX_ABI_VERSION 4
+#define DCX_MAX_CODEBOOKS 8 /* residual layers of the quantizer (dcx_set_num_codebooks) */
 
 enum {
   DCX_OK = 0,
@@ -43,7 +44,8 @@ typedef struct dcx_codec dcx_codec;
 
 /* Geometry of the model; mirrors configs/model_config.json (DistilCodec.__init__,
  * distilcodec/distil_codec.py:30-70).  Only the published geometry family is supported
- * (G=1, R=1, downsample factor 1, no template branch); others return DCX_ERR_INVALID_ARG. */
+ * (G=1, downsample factor 1, no template branch); others return DCX_ERR_INVALID_ARG.  The number of
+ * residual codebooks R (n_codebooks; 1 in the published model) is set with dcx_set_num_codebooks. */
 typedef struct dcx_config {
   int32_t sample_rate;          /* 24000 */
   int32_t n_fft, hop, win;      /* 1024, 256, 1024 (mel_spec.py) */
@@ -86,6 +88,18 @@ int dcx_set_tensor(dcx_codec* h, const char* name, const float* host_data, int32
  * E * W_out^T + b_out.  Blocking.  `with_generator` = 0 builds encode-side stages only. */
 int dcx_finalize(dcx_codec* h, int32_t with_generator);
 
+/* Residual VQ (ResidualVQ, residual_vq.py:140-259): R = n codebooks in a chain, layer k quantizing what
+ * layer k - 1 left over: r_0 = x_pjt_in, c_k = argmin_j |r_k - E_k[j]|^2 (exact, first index on ties),
+ * r_{k+1} = fl32(r_k - E_k[c_k]); quantized_fup = the fp32 sum of the E_k[c_k] in layer order; project_in
+ * and project_out are shared.  E_k is "quantizer.grvq.rvqs.0.layers.<k>._codebook.embed".
+ * dcx_set_num_codebooks: after dcx_create and before dcx_finalize (DCX_ERR_STATE afterwards), 1 <= n <=
+ * DCX_MAX_CODEBOOKS (else DCX_ERR_INVALID_ARG); the default is 1.  With R > 1 dcx_finalize needs every
+ * layer's codebook (DCX_ERR_MISSING_WEIGHT otherwise, never a shorter chain), and every `codes`
+ * argument below gains an innermost axis of R entries per frame ([B][T][R], [sum T][R]); with R = 1
+ * nothing changes. */
+int dcx_set_num_codebooks(dcx_codec* h, int32_t n);
+int32_t dcx_num_codebooks(const dcx_codec* h);
+
 /* Frames for a padded clip of n_samples (= raw length + 1, distil_codec.py:133-136):
  * T = floor((n_samples + 2*384 - 1024)/256) + 1. */
 int64_t dcx_num_frames(const dcx_codec* h, int64_t n_samples);
@@ -111,18 +125,21 @@ int dcx_encode(dcx_codec* h, const float* mel, int32_t batch, int64_t frames, fl
 /* DownsampleGRVQ.forward (grfvq.py:105-132) in eval mode: down conv + ConvNeXt block,
  * project_in (residual_vq.py:152), nearest-code search (vector_quantize_pytorch.py:41-45,
  * 496-506; first index on ties), gather, project_out (residual_vq.py:241), up ConvT1x1 +
- * ConvNeXt block.  codes: [B][T] int32 (required).  x_pjt_in / quantized_fup ([B][T][3584])
- * and quantized ([B][T][vq_dim]) may be NULL to skip them (codes-only fast path). */
+ * ConvNeXt block.  codes: [B][T][R] int32 (required; R = dcx_num_codebooks).  x_pjt_in /
+ * quantized_fup ([B][T][codebook_dim]) and quantized ([B][T][vq_dim]) may be NULL to skip them
+ * (codes-only fast path).  With R > 1 the search runs per layer on the fp32 residual, quantized_fup is
+ * the layers' sum and project_out a 1x1 conv on it (one codebook decodes through a table). */
 int dcx_vq_encode(dcx_codec* h, const float* feat, int32_t batch, int64_t frames, int32_t* codes,
                   float* x_pjt_in, float* quantized_fup, float* quantized,
                   void* workspace, size_t ws_bytes, void* stream);
 
-/* DownsampleGRVQ.decode (grfvq.py:141-146): codes [B][T] int32 -> z [B][T][vq_dim].
+/* DownsampleGRVQ.decode (grfvq.py:141-146): codes [B][T][R] int32 -> z [B][T][vq_dim].
  * Code -1 is the reference's masked code (residual_vq.py:120-127: fetched as code 0, then zeroed
- * before project_out), so its frame decodes project_out(0) = the project_out bias.  Other negative
+ * before project_out): it adds nothing to the frame's sum, so a frame whose layers are all -1
+ * decodes project_out(0) = the project_out bias.  Other negative
  * codes in [-codebook_size, -1) wrap to code + codebook_size, like the torch indexing of the
  * reference's gather (distil_codec.py:584-586, residual_vq.py:123).  Codes still outside
- * [0, codebook_size) read row 0 and are counted into *n_invalid (device int, may be NULL); the
+ * [0, codebook_size), in any layer, read row 0 and are counted into *n_invalid (device int, may be NULL); the
  * Python surface raises IndexError for them before calling, as torch indexing would. */
 int dcx_vq_decode(dcx_codec* h, const int32_t* codes, int32_t batch, int64_t frames, float* z,
                   int32_t* n_invalid, void* workspace, size_t ws_bytes, void* stream);
@@ -132,7 +149,7 @@ int dcx_generate(dcx_codec* h, const float* z, int32_t batch, int64_t frames, fl
                  void* workspace, size_t ws_bytes, void* stream);
 
 /* Whole path: audio -> mel -> encoder -> VQ -> decode(codes) -> generator (encode() followed
- * by decode_from_codes(), distil_codec.py:545-594).  codes [B][T] and wav [B][256*T] required. */
+ * by decode_from_codes(), distil_codec.py:545-594).  codes [B][T][R] and wav [B][256*T] required. */
 int dcx_encode_decode(dcx_codec* h, const float* audio, int32_t batch, int64_t n_samples,
                       int32_t* codes, float* wav, void* workspace, size_t ws_bytes, void* stream);
 
@@ -155,7 +172,7 @@ int dcx_encode_decode(dcx_codec* h, const float* audio, int32_t batch, int64_t n
  * kernels index: more than 2^31 - 1 samples or 2^20 frames (about 3.1 h of audio) in one call.
  * dcx_ragged_workspace_size: device workspace bytes of dcx_tokenize_ragged (0 for bad arguments).
  * dcx_tokenize_ragged: the caller uploads the table as is (plan_dev, device; plan_host, the host
- * copy, is read for the totals).  codes: int32 [sum T]; x_pjt_in / quantized_fup: [sum T][codebook_dim]
+ * copy, is read for the totals).  codes: int32 [sum T][R]; x_pjt_in / quantized_fup: [sum T][codebook_dim]
  * or NULL.  Stream-ordered, allocates nothing, never synchronises, and runs on the caller's stream
  * alone (no half-batch fork).  DCX_GEMM_X6 and DCX_GEMM_BF16; DCX_GEMM_F32 returns DCX_ERR_INVALID_ARG
  * (the packed intermediates are planes).  DCX_ERR_STATE before dcx_finalize and while split-K is on
@@ -173,7 +190,7 @@ int dcx_tokenize_ragged(dcx_codec* h, const float* audio_packed, const int32_t* 
  * dcx_vq_decode -> dcx_generate give for that clip ALONE.  (The padded calls reproduce the reference,
  * which pads a batch of code lists to the longest with code 0: the generator is conv-only, so there
  * the last samples of a short clip depend on what shares its batch.)  The layout is the padded one:
- * z [B][frames_max][vq_dim], codes [B][frames_max], wav [B][256 * frames_max]; lengths_dev is DEVICE
+ * z [B][frames_max][vq_dim], codes [B][frames_max][R], wav [B][256 * frames_max]; lengths_dev is DEVICE
  * memory, int32 [B], frames per clip, so one hipGraph captured for (batch, frames_max) serves any
  * lengths.  The kernels clamp each length to [0, frames_max]; validate on the host before the upload.
  *   wav[b][0 : 256 len_b)                the clip's samples;
@@ -326,6 +343,8 @@ int dcx_conv_set_h3(dcx_conv* c, int32_t on);
  *       LayerNorm (convnext_utils.py:186-213);
  *   "quantizer.downsample.0" / "quantizer.upsample.0": Conv1d / ConvTranspose1d + ConvNeXtBlock
  *       (grfvq.py:68-96); "quantizer.grvq.rvqs.0.project_in": Linear (residual_vq.py:152);
+ *   "quantizer.grvq.rvqs.0.project_out": Linear (residual_vq.py:138, 241), x [B][rows][codebook_dim] ->
+ *       y [B][rows][vq_dim], the 1x1 conv a chain of R > 1 codebooks decodes through;
  *   "generator.conv_pre": Conv1d (generators.py:121);
  *   "generator.ups.<i>": ConvTranspose1d, y [B][rows * rate][Cout] (generators.py:29-116);
  *   "generator.resblocks.<i>.blocks.<j>": ResBlock1 (convnext_utils.py:106-113), per-conv launches;
@@ -336,7 +355,7 @@ int dcx_conv_set_h3(dcx_conv* c, int32_t on);
  *       y [B][rows][1];
  *   "quantizer.search": nearest code (vector_quantize_pytorch.py:41-45, 496-506) of x_pjt_in rows
  *       x [B][rows][codebook_dim]; y = int32 codes [B][rows] (every mode: the exact nearest code of x
- *       as given; in bf16 mode through the pipeline's compact-operand prefilter).
+ *       as given; in bf16 mode through the pipeline's compact-operand prefilter); layer 0's codebook.
  * dcx_module_io reports a module's input channels, output channels (0: int32 codes) and output rows
  * per input row; unknown names return DCX_ERR_INVALID_ARG (and dcx_module_workspace_size 0).
  * dcx_module_forward takes the input's channel count and returns DCX_ERR_INVALID_ARG unless it is the
