@@ -63,6 +63,12 @@ _I64 = ctypes.c_int64
 _SZ = ctypes.c_size_t
 
 # name -> (restype, argtypes); must list every function declared in include/distilcodec_amd.h
+class ConvH3Out(ctypes.Structure):
+    """dcx_conv_h3_out (include/distilcodec_amd.h)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("y", "y_silu", "y_silu_h2", "y_ash", "y_amax", "res", "res_amax", "macc",
+                                               "macc_amax", "lens")] + [("epi", ctypes.c_int32), ("mean", ctypes.c_int32)]
+
+
 SIGNATURES = {
     "dcx_default_config": (None, [ctypes.POINTER(DcxConfig)]),
     "dcx_create": (ctypes.c_int, [ctypes.POINTER(DcxConfig), ctypes.POINTER(_P)]),
@@ -109,6 +115,8 @@ SIGNATURES = {
     "dcx_conv_forward": (ctypes.c_int, [_P, _I32, _P, _I32, _I64, _P, _P, _P, _I32, _P]),
     "dcx_conv_destroy": (None, [_P]),
     "dcx_conv_last_kernel": (ctypes.c_char_p, [_P]),
+    "dcx_conv_forward_h3": (ctypes.c_int, [_P, _P, _I32, ctypes.c_int64, _P, _P]),
+    "dcx_epi_form_launches": (ctypes.c_int, [ctypes.POINTER(ctypes.c_int64), _I32, _I32]),
     "dcx_conv_set_knob": (ctypes.c_int, [_P, ctypes.c_char_p, _I32]),
     "dcx_conv_set_h3": (ctypes.c_int, [_P, _I32]),
     "dcx_module_workspace_size": (_SZ, [_P, ctypes.c_char_p, _I32, _I64]),

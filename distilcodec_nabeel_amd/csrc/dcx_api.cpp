@@ -558,22 +558,25 @@ int dcx_conv_create(const float* weight, const float* bias, int32_t cin, int32_t
   return DCX_OK;
 }
 
-int dcx_conv_forward(dcx_conv* c, int32_t gemm_mode, const float* x, int32_t batch, int64_t lin, float* y,
-                     float* y_silu, const float* res, int32_t epi, void* stream) {
-  if (!c || !x || batch <= 0 || lin <= 0 || (!y && !y_silu)) return DCX_ERR_INVALID_ARG;
-  if (epi != dcx::EPI_BIAS && epi != dcx::EPI_GELU && epi != dcx::EPI_RES) return DCX_ERR_INVALID_ARG;
-  if (epi == dcx::EPI_RES && !res) return DCX_ERR_INVALID_ARG;
+}  // extern "C"
+
+// The primitive's call: the input in the form its GEMM mode takes, then `outputs(cc, h3)` fills in the
+// call's outputs and epilogue (h3: the conv runs in h3 arithmetic, cc.x.r holding the input's range)
+template <class Outputs>
+static int conv_forward(dcx_conv* c, int32_t gemm_mode, const float* x, int32_t batch, int64_t lin, void* stream,
+                        Outputs outputs) {
   dcx_codec* h = &c->scratch;
   h->gemm_mode = gemm_mode;
   hipStream_t s = (hipStream_t)stream;
   CAct xa(x, nullptr);
+  bool h3 = false;
   if (gemm_mode != DCX_GEMM_F32 && gemm_mode != DCX_GEMM_X6 && gemm_mode != DCX_GEMM_BF16) return DCX_ERR_INVALID_ARG;
   if (gemm_mode != DCX_GEMM_F32 && !f32_input_ok(c->w)) {
     const size_t need = (size_t)batch * lin * c->w.cin * 3;
     if (!grow(c->planes, c->planes_cap, need)) return DCX_ERR_OOM;
     // h3 (dcx_conv_set_h3): the input in the h2 layout, range-scaled as ensure_planes does for a
     // caller's tensor: per clip (exact max) for the tap convs, per row for a one-tap Conv1d
-    const bool h3 = c->h3 && (c->w.taps >= 2 ? takes_h3_conv(h, c->w, lin) : takes_h3(h, c->w));
+    h3 = c->h3 && (c->w.taps >= 2 ? takes_h3_conv(h, c->w, lin) : takes_h3(h, c->w));
     if (h3) {
       const long long rows = (long long)batch * lin;
       const size_t words = (size_t)batch + (size_t)std::max<long long>(batch, rows);
@@ -598,11 +601,52 @@ int dcx_conv_forward(dcx_conv* c, int32_t gemm_mode, const float* x, int32_t bat
     xa.p = c->planes;
   }
   ConvCall cc = framed(xa, batch, (int)lin, c->w.cin);
-  cc.y = y;
-  cc.y2 = y_silu;
-  cc.res = res;
-  cc.epi = epi;
-  return run_conv(h, c->w, cc, s);
+  const int code = outputs(cc, h3);
+  return code != DCX_OK ? code : run_conv(h, c->w, cc, s);
+}
+
+extern "C" {
+
+int dcx_conv_forward(dcx_conv* c, int32_t gemm_mode, const float* x, int32_t batch, int64_t lin, float* y,
+                     float* y_silu, const float* res, int32_t epi, void* stream) {
+  if (!c || !x || batch <= 0 || lin <= 0 || (!y && !y_silu)) return DCX_ERR_INVALID_ARG;
+  if (epi != dcx::EPI_BIAS && epi != dcx::EPI_GELU && epi != dcx::EPI_RES) return DCX_ERR_INVALID_ARG;
+  if (epi == dcx::EPI_RES && !res) return DCX_ERR_INVALID_ARG;
+  return conv_forward(c, gemm_mode, x, batch, lin, stream, [&](ConvCall& cc, bool) -> int {
+    cc.y = y;
+    cc.y2 = y_silu;
+    cc.res = res;
+    cc.epi = epi;
+    return DCX_OK;
+  });
+}
+
+int dcx_conv_forward_h3(dcx_conv* c, const float* x, int32_t batch, int64_t lin, const dcx_conv_h3_out* o, void* stream) {
+  if (!c || !x || !o || batch <= 0 || lin <= 0 || c->w.taps < 2 || c->w.phases != 1) return DCX_ERR_INVALID_ARG;
+  if (o->epi != dcx::EPI_BIAS && o->epi != dcx::EPI_RES) return DCX_ERR_INVALID_ARG;
+  if (o->mean < dcx::MEAN_NONE || o->mean > dcx::MEAN_LAST || (o->mean != dcx::MEAN_NONE && !o->macc)) return DCX_ERR_INVALID_ARG;
+  if (o->epi == dcx::EPI_RES && (!o->res || !o->res_amax)) return DCX_ERR_INVALID_ARG;
+  if (o->mean >= dcx::MEAN_MID && !o->macc_amax) return DCX_ERR_INVALID_ARG;
+  if (o->y_silu_h2 && !o->y_ash) return DCX_ERR_INVALID_ARG;
+  return conv_forward(c, DCX_GEMM_X6, x, batch, lin, stream, [&](ConvCall& cc, bool h3) -> int {
+    if (!h3) return fail(&c->scratch, DCX_ERR_INVALID_ARG, "dcx_conv_forward_h3: not an h3 conv (dcx_conv_set_h3, Cout % 128)");
+    cc.y = o->y;
+    cc.y2 = o->y_silu;
+    cc.y6s = o->y_silu_h2;
+    cc.ys_lay = dcx::LAYOUT_H2;
+    cc.res = o->res;
+    cc.macc = o->macc;
+    cc.epi = o->epi;
+    cc.mean = o->mean;
+    // |v| <= g max|x| + max|b| (+ max|res|, + max|macc|: the mean's third is left out, a looser bound)
+    cc.yb = prog_conv(c->w, cc.x.r);
+    if (o->res) prog_add(cc.yb, 1.0f, Rng{nullptr, 0, o->res_amax, 0.f});
+    if (o->mean >= dcx::MEAN_MID) prog_add(cc.yb, 1.0f, Rng{nullptr, 0, o->macc_amax, 0.f});
+    cc.y_amax = o->y_amax;
+    cc.y_ash = o->y_silu_h2 ? o->y_ash : nullptr;
+    cc.ragged(o->lens, (int)lin);
+    return DCX_OK;
+  });
 }
 
 void dcx_conv_destroy(dcx_conv* c) {
@@ -614,6 +658,14 @@ void dcx_conv_destroy(dcx_conv* c) {
 }
 
 const char* dcx_conv_last_kernel(const dcx_conv* c) { return c ? c->scratch.last_kname : ""; }
+
+int dcx_epi_form_launches(int64_t* counts, int32_t n, int32_t reset) {
+  if (!counts || n != dcx::kEpiFormCounters) return DCX_ERR_INVALID_ARG;
+  long long v[dcx::kEpiFormCounters];
+  dcx::epi_form_launches(v, reset != 0);
+  for (int i = 0; i < n; ++i) counts[i] = v[i];
+  return DCX_OK;
+}
 
 int dcx_conv_set_knob(dcx_conv* c, const char* name, int32_t value) {
   if (!c || !name) return DCX_ERR_INVALID_ARG;

@@ -232,6 +232,226 @@ __device__ __forceinline__ EpiPre epi_range_pre(const ConvParams& p, const ConvP
   return e;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Compile-time epilogue forms (the h3 kernels).  epilogue_lds decides everything per row at run time:
+// epi, mean_mode, which of y / y2 / y6 / y6s exist and their layouts, round_bf16, range tracking.  In
+// the unrolled rows that is ~1100 branches, and because the number of stores of a row then depends on
+// the path taken, hipcc can place only vmcnt(0) before a later row's loaded values: every such wait
+// also drains the stores of the rows before it.  An EpiForm fixes those fields, and epilogue_form is
+// the same arithmetic, operation by operation, for a fixed form.  EpiGeneric keeps epilogue_lds.
+// y6h / y6sh: y6 / y6s exist and are LAYOUT_H2 (no form writes planes or compact images); rowwise:
+// the h2 output's bound is per row (one-tap convs).  round_bf16 is 0 in every form.
+// ---------------------------------------------------------------------------------------------
+struct EpiGeneric {
+  static constexpr bool fixed = false;
+};
+template <int EPI, int MEAN, bool Y, bool Y2, bool Y6H, bool Y6SH, bool TRACK, bool ROWWISE = false>
+struct EpiForm {
+  static constexpr bool fixed = true;
+  static constexpr int epi = EPI, mean = MEAN;
+  static constexpr bool y = Y, y2 = Y2, y6h = Y6H, y6sh = Y6SH, track = TRACK, rowwise = ROWWISE;
+};
+// (host) whether p is exactly the form F: the launchers pick an instantiation with it
+template <typename F>
+inline bool epi_form_is(const ConvParams& p) {
+  const bool h2o = F::y6h || F::y6sh;
+  return p.epi == F::epi && p.mean_mode == F::mean && !p.round_bf16 && (p.y != nullptr) == F::y &&
+         (p.y2 != nullptr) == F::y2 && (p.y6 != nullptr) == F::y6h && (p.y6s != nullptr) == F::y6sh &&
+         (!p.y6 || p.y_layout == LAYOUT_H2) && (!p.y6s || p.ys_layout == LAYOUT_H2) && (p.y_amax != nullptr) == F::track &&
+         (h2o ? (p.yb.rowwise != 0) == F::rowwise : true) && (F::epi != EPI_GELU || p.w6 != nullptr) &&
+         (F::mean == MEAN_NONE || p.macc != nullptr);
+}
+
+// epilogue_lds for a fixed form F (its template arguments, and the meaning of every name, are
+// epilogue_lds's).  Besides the branches, the order of the memory operations differs:
+//  * a batch's rows are all finished into registers (LDS read, bias, residual / gamma / mean add)
+//    before its first store, so the batch's loaded values are consumed before any store is issued;
+//  * the next batch's residual / mean rows are loaded before the current batch's stores, so their
+//    wait is vmcnt(stores after them), not 0;
+//  * a pass whose rows all lie inside Lq (workgroup-uniform) runs without the per-row end test: a
+//    skipped row would again make the store count depend on the path.
+// Aliasing (the ResBlock state and the mean accumulator are updated in place): a thread stores only
+// elements it has already loaded, and the rows it loads early are rows it has not stored yet.
+template <int BM, int BN, int WM, int WN, int LDS_FLOATS, int NT, int RROW, bool RAG, typename F, typename AccT>
+__device__ __forceinline__ void epilogue_form(const ConvParams& p, const ConvParams& pr, AccT& acc, int q0, int co0, int b,
+                                              int ph, float* smem, const EpiPre& pre) {
+  constexpr int WR = BM / WM, WC = BN / WN;
+  static_assert(sizeof(acc[0][0]) == 16 && sizeof(acc) == WR * WC * 4 / 64, "16 x 16 accumulator blocks");
+  constexpr int LDSW = BN + 4;
+  constexpr int RPP = (BM * LDSW <= LDS_FLOATS) ? BM
+                      : (BM / 2 * LDSW <= LDS_FLOATS) ? BM / 2
+                      : (BM / 4 * LDSW <= LDS_FLOATS) ? BM / 4 : WR;
+  static_assert(RPP % WR == 0 && RPP * LDSW <= LDS_FLOATS, "epilogue pass does not fit LDS");
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave / WN, wn = wave % WN;
+  const long long ob = (long long)b * p.y_bstride;
+  constexpr bool RIN = RROW & 1, ROUT = RROW & 2;
+  constexpr bool h2o = F::y6h || F::y6sh, h2row = ROUT && h2o && F::rowwise;
+  constexpr bool need_r = F::epi == EPI_GAMMA_RES || F::epi == EPI_RES;
+  constexpr bool need_m = F::mean == MEAN_MID || F::mean == MEAN_LAST;
+  // only the last member of a mean chain has outputs of its own
+  static_assert(!((F::mean == MEAN_FIRST || F::mean == MEAN_MID) && (F::y || F::y2 || h2o || F::track)), "mean form");
+  unsigned short* const y6 = F::y6h ? p.y6 + ob * 2 : nullptr;
+  unsigned short* const y6s = F::y6sh ? p.y6s + ob * 2 : nullptr;
+  const float osc = __builtin_bit_cast(
+      float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, __builtin_ldexpf(1.0f, h2o && !h2row ? pre.osh : 0))));
+  float vmax = 0.f;
+  const int lq_live = RAG ? clip_rows(pr.clip_len, pr.len_mul, b, p.Lq) : p.Lq;
+  constexpr int G = 8, NH = 2;
+  static_assert(NT % (BN / G) == 0, "each thread keeps one channel group");
+  const int cg = (tid % (BN / G)) * G, trow = tid / (BN / G), co = co0 + cg;
+  const int hsw = (lane >> 3) & 1;  // LDS read order of the two halves (epilogue_lds)
+  f32x4 bias4[NH], gamma4[NH];
+#pragma unroll
+  for (int h = 0; h < NH; ++h) {
+    bias4[h] = p.bias ? *reinterpret_cast<const f32x4*>(p.bias + co + 4 * h) : f32x4{0.f, 0.f, 0.f, 0.f};
+    gamma4[h] = F::epi == EPI_GAMMA_RES ? *reinterpret_cast<const f32x4*>(p.gamma + co + 4 * h) : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+  constexpr int RSTEP = NT / (BN / G), ROWS_T = RPP / RSTEP;
+  static_assert(RPP % RSTEP == 0, "epilogue rows per thread");
+  constexpr auto div_cap = [](int n, int cap) {
+    int d = n < cap ? n : cap;
+    while (n % d) --d;
+    return d;
+  };
+  // batches of 4 rows, 2 where residual / mean rows are loaded (16-byte loads, 8 VGPRs per row and
+  // tensor): two batches' rows are in registers at a time here, and with 4 the 256 x 256 residual
+  // forms spilled 52-176 bytes, reloaded inside the row code.  (EpiPw1's per-row range words, rin /
+  // rbnd, are one VGPR each: it keeps 4.)
+  constexpr int IB = div_cap(ROWS_T, need_r || need_m ? 4 / NH : 8 / NH);
+  auto row_bound = [&](int q) { return fmaf(pr.yb.g[0], fmaxf(pr.yb.m[0][(long long)b * p.Lq + q], pr.yb.f[0]), pr.yb.c); };
+
+  auto pass = [&](int r0, auto fullt) {
+    constexpr bool FULL = decltype(fullt)::value;  // every row of the pass lies inside Lq
+    f32x4 r[IB][NH], m[IB][NH];
+    float rin[RIN ? IB : 1], rbnd[h2row ? IB : 1];
+    auto load = [&](int rb) {  // rows past the end clamped, as in epilogue_lds
+#pragma unroll
+      for (int k = 0; k < IB; ++k) {
+        const int qq = q0 + r0 + trow + (rb + k) * RSTEP;
+        const int q = FULL ? qq : min(qq, p.Lq - 1);
+        const long long o = ob + ((long long)q * p.out_mul + ph) * p.ldy + co;
+#pragma unroll
+        for (int h = 0; h < NH; ++h) {
+          if constexpr (need_r) r[k][h] = *reinterpret_cast<const f32x4*>(p.res + o + 4 * h);
+          if constexpr (need_m) m[k][h] = *reinterpret_cast<const f32x4*>(p.macc + o + 4 * h);
+        }
+        if constexpr (RIN) rin[k] = pr.x_ash_row ? __builtin_ldexpf(1.0f, -pr.x_ash_row[(long long)b * p.Lin + q]) : 1.0f;
+        if constexpr (h2row) rbnd[k] = row_bound(q);
+      }
+    };
+    load(0);
+    __syncthreads();  // acc rows [r0, r0 + RPP) of the tile -> LDS (lane holds column l & 15, rows 4 (l >> 4) + e)
+    if (wm * WR >= r0 && wm * WR < r0 + RPP) {
+#pragma unroll
+      for (int i = 0; i < WR / 16; ++i)
+#pragma unroll
+        for (int j = 0; j < WC / 16; ++j)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int row = wm * WR + i * 16 + 4 * (lane >> 4) + e - r0;
+            smem[row * LDSW + wn * WC + j * 16 + (lane & 15)] = acc[i][j][e];
+          }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int rb = 0; rb < ROWS_T; rb += IB) {
+      f32x4 x[IB][NH];
+      float rsc[IB];
+      // phase 1: every row of the batch finished into registers
+#pragma unroll
+      for (int k = 0; k < IB; ++k) {
+        const int rl = trow + (rb + k) * RSTEP;
+        const int q = q0 + r0 + rl;
+        const bool dead = RAG && q >= lq_live;  // beyond the clip's length (its own zero padding)
+        const float rin_ = RIN ? rin[RIN ? k : 0] : 1.0f;
+        const f32x4 u = *reinterpret_cast<const f32x4*>(smem + rl * LDSW + cg + 4 * hsw);
+        const f32x4 v = *reinterpret_cast<const f32x4*>(smem + rl * LDSW + cg + 4 * (1 - hsw));
+        x[k][0] = (hsw ? v : u) * rin_ + bias4[0];
+        x[k][1] = (hsw ? u : v) * rin_ + bias4[1];
+#pragma unroll
+        for (int h = 0; h < NH; ++h) {
+          if constexpr (F::epi == EPI_GELU) {
+#pragma unroll
+            for (int e = 0; e < 4; e += 2) {
+              const f32x2 g = gelu_bf16_f2(f32x2{x[k][h][e], x[k][h][e + 1]});
+              x[k][h][e] = g[0];
+              x[k][h][e + 1] = g[1];
+            }
+          } else if constexpr (F::epi == EPI_GAMMA_RES) {
+            x[k][h] = r[k][h] + gamma4[h] * x[k][h];
+          } else if constexpr (F::epi == EPI_RES) {
+            x[k][h] = r[k][h] + x[k][h];
+          } else {
+            static_assert(F::epi == EPI_BIAS, "epilogue form");
+          }
+          if (dead) x[k][h] = f32x4{0.f, 0.f, 0.f, 0.f};
+          if constexpr (F::mean == MEAN_MID) x[k][h] = dead ? x[k][h] : m[k][h] + x[k][h];
+          if constexpr (F::mean == MEAN_LAST) x[k][h] = dead ? x[k][h] : (m[k][h] + x[k][h]) / 3.0f;
+        }
+        rsc[k] = osc;
+        if constexpr (h2row) rsc[k] = rbnd[k];  // the row's bound; its scale is taken in phase 2
+      }
+      // the next batch's loads ahead of this batch's stores
+      if (rb + IB < ROWS_T) load(rb + IB);
+      // phase 2: SiLU, split and stores, row by row
+#pragma unroll
+      for (int k = 0; k < IB; ++k) {
+        const int q = q0 + r0 + trow + (rb + k) * RSTEP;
+        if (!FULL && q >= p.Lq) continue;
+        const long long orow = (long long)q * p.out_mul + ph;
+        const long long o = ob + orow * p.ldy + co;
+        if constexpr (F::mean == MEAN_FIRST || F::mean == MEAN_MID) {
+#pragma unroll
+          for (int h = 0; h < NH; ++h) *reinterpret_cast<f32x4*>(p.macc + o + 4 * h) = x[k][h];
+          continue;
+        }
+        float sc = rsc[k];  // the h2 output's scale for this row
+        if constexpr (h2row) {
+          const float bnd = rsc[k];
+          const int sh = h2_shift(bnd);
+          sc = __builtin_ldexpf(1.0f, sh);
+          if (cg == 0 && pr.y_ash) pr.y_ash[(long long)b * p.Lq + q] = sh;
+          if (pr.rflag && !(bnd <= 3.0e38f)) atomicOr(pr.rflag, RANGE_NONFINITE);
+        }
+        if constexpr (F::track) {
+          const float ts = h2row ? sc : 1.0f;
+#pragma unroll
+          for (int h = 0; h < NH; ++h)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) vmax = fmaxf(vmax, fabsf(x[k][h][e]) * ts);
+        }
+        if constexpr (F::y) {
+#pragma unroll
+          for (int h = 0; h < NH; ++h) *reinterpret_cast<f32x4*>(p.y + o + 4 * h) = x[k][h];
+        }
+        float xv[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) xv[e] = x[k][e >> 2][e & 3];
+        if constexpr (F::y6h) store_h2_8<false>(y6, orow, p.Cout, co, xv, sc);
+        if constexpr (F::y2 || F::y6sh) {
+          float sv[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) sv[e] = silu_f(xv[e]);
+          if constexpr (F::y2) {
+            *reinterpret_cast<f32x4*>(p.y2 + o) = f32x4{sv[0], sv[1], sv[2], sv[3]};
+            *reinterpret_cast<f32x4*>(p.y2 + o + 4) = f32x4{sv[4], sv[5], sv[6], sv[7]};
+          }
+          if constexpr (F::y6sh) store_h2_8<false>(y6s, orow, p.Cout, co, sv, sc);
+        }
+      }
+    }
+  };
+#pragma unroll 1
+  for (int r0 = 0; r0 < BM; r0 += RPP) {
+    if (q0 + r0 + RPP <= p.Lq) pass(r0, std::true_type{});
+    else pass(r0, std::false_type{});
+  }
+  if constexpr (F::track)  // (rowwise: vmax holds scaled values, and pr.y_amax is not recorded)
+    range_report_wg(vmax, h2row ? nullptr : pr.y_amax, b, h2row ? 65504.0f : h2o ? 65504.0f / osc : __builtin_inff(),
+                    pr.rflag, pre.acur, smem, NT);
+}
+
 // RROW: which per-row range forms a kernel may meet (round 6).  Bit 0: an h2 input scaled per row
 // (x_ash_row: the h3 one-tap kernels), loaded with the batch's rows; bit 1: a rowwise bound of an h2
 // output (yb.rowwise: one-tap kernels).  Tap convs pass 0, which keeps these registers out of their
@@ -242,9 +462,17 @@ __device__ __forceinline__ EpiPre epi_range_pre(const ConvParams& p, const ConvP
 // most of a step, are instantiated both ways and launched by whether the call has lengths, so the
 // padded path runs the code it ran before the lengths existed (with the null-pointer select alone the
 // C2 step paid 0.6-1.2 %, DESIGN.md §5 "Ragged decode"); every other kernel keeps the select.
-template <int BM, int BN, int WM, int WN, int LDS_FLOATS, int NT, int RROW = 2, bool RAG = true, typename AccT>
+// F: EpiGeneric, or an EpiForm the caller has matched on the host (epi_form_is): epilogue_form.
+template <int BM, int BN, int WM, int WN, int LDS_FLOATS, int NT, int RROW = 2, bool RAG = true, typename F = EpiGeneric,
+          typename AccT>
 __device__ __forceinline__ void epilogue_lds(const ConvParams& p, const ConvParams& pr, AccT& acc, int q0, int co0,
                                              int b, int ph, float* smem, const EpiPre* pre = nullptr) {
+#ifndef DCX_EPI4  // (the A/B builds of 4-channel groups keep the generic epilogue everywhere)
+  if constexpr (F::fixed) {
+    epilogue_form<BM, BN, WM, WN, LDS_FLOATS, NT, RROW, RAG, F>(p, pr, acc, q0, co0, b, ph, smem, *pre);
+    return;
+  }
+#endif
   constexpr int WR = BM / WM, WC = BN / WN;
   constexpr int TM = WR / 32, TN = WC / 32;
   constexpr bool M16 = sizeof(acc[0][0]) == 16;

@@ -1,5 +1,7 @@
 // The h3 conv kernels (fp16 "h2" operands, three products): conv_gemm_x3dq / x3dm and the wide-tile
 // conv_gemm_x3dw, their grouped forms, tile choice and launchers.  Fragment maps: dcx_conv.hip.
+#include <atomic>
+
 #include "dcx_conv_common.h"
 #include "dcx_conv_launch.h"
 #include "dcx_conv_pingpong.h"
@@ -32,6 +34,54 @@ DCX_DIAG_FILE(h3)
 // The A buffer of chunk c + 2 is issued taps - 2 segments after chunk c's last read: taps >= 3.
 // ---------------------------------------------------------------------------------------------
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+// The epilogue forms (dcx_conv_common.h EpiForm) the host code produces on these kernels in x6 mode;
+// anything else (bf16 rounding, planes or compact outputs, DCX_EPI_GENERIC=1) runs EpiGeneric.
+//                       epi            mean        y      y2     y6h    y6sh   track  rowwise
+using EpiC1 = EpiForm<EPI_BIAS, MEAN_NONE, false, false, false, true, true>;        // conv_pre, a pair's c1: silu in h2
+using EpiUp = EpiForm<EPI_BIAS, MEAN_NONE, true, false, false, true, true>;         // ConvT: fp32 and silu in h2
+using EpiC2 = EpiForm<EPI_RES, MEAN_NONE, true, false, false, true, true>;          // a pair's c2: state and silu in h2
+using EpiMeanF = EpiForm<EPI_RES, MEAN_FIRST, false, false, false, false, false>;   // ParallelBlock mean, first ResBlock
+using EpiMeanM = EpiForm<EPI_RES, MEAN_MID, false, false, false, false, false>;     // ... the middle ones
+using EpiMeanLH = EpiForm<EPI_RES, MEAN_LAST, false, false, false, true, true>;     // ... last: silu(mean) in h2
+using EpiMeanLF = EpiForm<EPI_RES, MEAN_LAST, false, true, false, false, true>;     // ... last: silu(mean) in fp32
+using EpiPw1 = EpiForm<EPI_GELU, MEAN_NONE, false, false, true, false, false, true>;  // ConvNeXt pwconv1: h2, row ranges
+using EpiPw2 = EpiForm<EPI_GAMMA_RES, MEAN_NONE, true, false, false, false, false>;   // ConvNeXt pwconv2: fp32 stream
+
+// Launch counts of the conv_gemm_x3dw kernels by epilogue form, process-wide (epi_form_launches: the
+// kernel names do not tell the forms apart, so the tests read these): [0 .. 8] the forms in the order
+// above, [kEpiFormCounters - 1] EpiGeneric.
+static std::atomic<long long> g_form_launches[kEpiFormCounters];
+template <typename F>
+constexpr int epi_form_id() {
+  return std::is_same_v<F, EpiC1> ? 0 : std::is_same_v<F, EpiUp> ? 1 : std::is_same_v<F, EpiC2> ? 2
+       : std::is_same_v<F, EpiMeanF> ? 3 : std::is_same_v<F, EpiMeanM> ? 4 : std::is_same_v<F, EpiMeanLH> ? 5
+       : std::is_same_v<F, EpiMeanLF> ? 6 : std::is_same_v<F, EpiPw1> ? 7 : std::is_same_v<F, EpiPw2> ? 8
+                                                                                                     : kEpiFormCounters - 1;
+}
+void epi_form_launches(long long* out, bool reset) {
+  for (int i = 0; i < kEpiFormCounters; ++i) out[i] = reset ? g_form_launches[i].exchange(0) : g_form_launches[i].load();
+}
+// f(F{}) for the first of Fs that p is (epi_form_is), else, and under Knobs::epi_generic, f(EpiGeneric{})
+template <typename... Fs, typename Fn>
+static hipError_t with_epi_form(const ConvParams& p, bool generic, Fn&& f) {
+  hipError_t e = hipSuccess;
+  bool done = false;
+  if (!generic)
+    ((done = done || (epi_form_is<Fs>(p) ? (++g_form_launches[epi_form_id<Fs>()], e = f(Fs{}), true) : false)), ...);
+  if (!done) ++g_form_launches[kEpiFormCounters - 1];
+  return done ? e : f(EpiGeneric{});
+}
+// A grouped launch runs one form: the members' (the host groups a stage's c1 convs, or its c2 convs,
+// which differ in weights and buffers only); members of different forms run EpiGeneric.
+static bool group_generic(const ConvGroup& g) {
+  if (knobs(g.p[0]).epi_generic) return true;
+  for (int k = 1; k < kMaxGroup; ++k)
+    if (g.start[k + 1] > g.start[k] && !(epi_form_is<EpiC1>(g.p[k]) == epi_form_is<EpiC1>(g.p[0]) &&
+                                         epi_form_is<EpiC2>(g.p[k]) == epi_form_is<EpiC2>(g.p[0])))
+      return true;
+  return false;
+}
 
 // Ragged batches: a tile wholly beyond its clip's length writes its zeros and the caller leaves
 // (workgroup-uniform; nothing has been issued and no barrier met yet, and of the tile's geometry
@@ -210,7 +260,7 @@ __global__ void __launch_bounds__(512, 2) conv_gemm_x3dq_group(const ConvGroup g
 // the end of MEM1(s + 1), before the barrier that opens MEM0(s + 1), their first reader.
 // BN = 256: 256 x 256 tiles of 64 x 128 wave tiles (Cout % 256 == 0); BN = 128: 384 x 128 tiles of
 // 48 x 128 wave tiles (the C = 128 stage: 72 MFMAs per segment against x3dq's 48).
-template <int HALO, bool SPLIT, int BN = 256, bool RAG = false, bool GROUPED = false>
+template <int HALO, bool SPLIT, int BN = 256, bool RAG = false, bool GROUPED = false, typename F = EpiGeneric>
 __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams& pr, const int wg, const int b, const int ph) {
   constexpr int BM = BN == 256 ? 256 : 384, WN = BN / 128, WM = 8 / WN;
   constexpr int WR = BM / WM, WC = 128, TM = WR / 16, TN = WC / 16;
@@ -224,6 +274,7 @@ __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams&
   static_assert(LDS_B + 16 <= 160 * 1024, "LDS");
   __shared__ __attribute__((aligned(16))) unsigned short lds[LDS_B / 2 + 8];  // + group 1's read counter
   unsigned int* const rd_cnt = reinterpret_cast<unsigned int*>(lds + LDS_B / 2);
+  DCX_TILET(tile_t0);
 
   // (its own geometry preamble, not tile_geo: with the shared one the epilogues of the 256 x 256 forms
   // spilled 4-8 bytes more, the ragged or the padded ones depending on where the dead-tile test stood)
@@ -368,6 +419,7 @@ __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams&
       __builtin_ldexpf(1.0f, -(p.w3_shift + (pr.x_ash ? pr.x_ash[b] : pr.x_ash_c))))));
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   seg_barrier();
+  DCX_TILET(tile_t1);
   in_loop = true;
 #ifdef DCX_SEG_DIAG
   unsigned long long sd[6] = {};
@@ -448,28 +500,30 @@ __device__ __forceinline__ void x3dw_tile(const ConvParams& p, const ConvParams&
   }
 #endif
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  DCX_TILET(tile_t2);
   // undo the weight and the input's range scaling (powers of two: exact)
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
     for (int j = 0; j < TN; ++j) acc[i][j] *= unscale;
-  epilogue_lds<BM, BN, WM, WN, LDS_B / 4, 512, HALO == 0 ? 3 : 0, RAG>(p, pr, acc, q0, co0, b, ph, reinterpret_cast<float*>(lds), &epre);
+  epilogue_lds<BM, BN, WM, WN, LDS_B / 4, 512, HALO == 0 ? 3 : 0, RAG, F>(p, pr, acc, q0, co0, b, ph, reinterpret_cast<float*>(lds), &epre);
+  DCX_TILE_END(nsteps);
 }
 
-template <int HALO, bool SPLIT, int BN = 256, bool RAG = false>
+template <int HALO, bool SPLIT, int BN = 256, bool RAG = false, typename F = EpiGeneric>
 __global__ void __launch_bounds__(512, 2) conv_gemm_x3dw(const ConvParams p) {
   constexpr int BM = BN == 256 ? 256 : 384;
   int wg, b, ph;
   flat_tile(((p.Lq + BM - 1) / BM) * (p.Cout / BN), p.batch, wg, b, ph);
-  x3dw_tile<HALO, SPLIT, BN, RAG>(p, p, wg, b, ph);
+  x3dw_tile<HALO, SPLIT, BN, RAG, false, F>(p, p, wg, b, ph);
 }
 
-template <bool SPLIT, int BN = 256, bool RAG = false>
+template <bool SPLIT, int BN = 256, bool RAG = false, typename F = EpiGeneric>
 __global__ void __launch_bounds__(512, 2) conv_gemm_x3dw_group(const ConvGroup g) {
   ConvParams p;
   int local, b;
   const ConvParams& pr = group_member(g, p, local, b);
-  x3dw_tile<64, SPLIT, BN, RAG, true>(p, pr, local, b, 0);
+  x3dw_tile<64, SPLIT, BN, RAG, true, F>(p, pr, local, b, 0);
 }
 
 // Whether conv_gemm_x3dq<bn> (taps >= 3 with a halo) or conv_gemm_x3dm<bn> (one tap) takes an h3
@@ -510,6 +564,8 @@ hipError_t launch_x3dq(const ConvParams& p, int batch, int phases, hipStream_t s
     if (kname) *kname = BN == 256 ? "conv_gemm_x3dm<128,256>" : "conv_gemm_x3dm<256,128>";
     return launch_flat<BM, BN>(conv_gemm_x3dq<BN, 0>, p, batch, phases, 512, s);
   }
+  // (these tiles run EpiGeneric: the tap convs come here under DCX_H3_BN only, and no conv of the
+  // model is a one-tap conv with Cout % 256 != 0)
   if (kname) *kname = BN == 256 ? "conv_gemm_x3dq<128,256,halo>" : "conv_gemm_x3dq<256,128,halo>";
   if (p.clip_len) return launch_flat<BM, BN>(conv_gemm_x3dq<BN, 64, true>, p, batch, phases, 512, s);  // ragged batch
   return launch_flat<BM, BN>(conv_gemm_x3dq<BN, 64>, p, batch, phases, 512, s);
@@ -518,69 +574,75 @@ hipError_t launch_x3dq(const ConvParams& p, int batch, int phases, hipStream_t s
 template hipError_t launch_x3dq<256>(const ConvParams&, int, int, hipStream_t, const char**);
 template hipError_t launch_x3dq<128>(const ConvParams&, int, int, hipStream_t, const char**);
 
+// A tap conv on conv_gemm_x3dw's BM x BN tiles, ragged or not, in its epilogue form.  The forms are
+// instantiated for the shipped DMA split only (Knobs::h3_split = 0, an A/B switch, runs EpiGeneric).
+template <int BM, int BN, bool RAG>
+static hipError_t launch_x3dw_halo(const ConvParams& p, bool sp, int batch, int phases, hipStream_t s) {
+  if (!sp) {
+    ++g_form_launches[kEpiFormCounters - 1];
+    return launch_flat<BM, BN>(conv_gemm_x3dw<64, false, BN, RAG>, p, batch, phases, 512, s);
+  }
+  return with_epi_form<EpiC1, EpiUp, EpiC2, EpiMeanF, EpiMeanM, EpiMeanLH, EpiMeanLF>(p, knobs(p).epi_generic, [&](auto f) {
+    return launch_flat<BM, BN>(conv_gemm_x3dw<64, true, BN, RAG, decltype(f)>, p, batch, phases, 512, s);
+  });
+}
+
 // bsel (x3dq_bn): 384 = the 384 x 128 tiles (the C = 128 stage), 512 = the 256 x 256 tiles
 hipError_t launch_x3dw(const ConvParams& p, int bsel, int batch, int phases, hipStream_t s, const char** kname) {
   const bool sp = knobs(p).h3_split;
-  if (p.clip_len) {  // ragged batch: the length-aware instantiations (tap convs)
-    if (p.taps == 1) return hipErrorNotSupported;
-    if (bsel == 384) {
-      if (kname) *kname = "conv_gemm_x3dw<384,128,halo>";
-      return sp ? launch_flat<384, 128>(conv_gemm_x3dw<64, true, 128, true>, p, batch, phases, 512, s)
-                : launch_flat<384, 128>(conv_gemm_x3dw<64, false, 128, true>, p, batch, phases, 512, s);
-    }
-    if (kname) *kname = "conv_gemm_x3dw<256,256,halo>";
-    return sp ? launch_flat<256, 256>(conv_gemm_x3dw<64, true, 256, true>, p, batch, phases, 512, s)
-              : launch_flat<256, 256>(conv_gemm_x3dw<64, false, 256, true>, p, batch, phases, 512, s);
-  }
+  if (p.clip_len && p.taps == 1) return hipErrorNotSupported;  // ragged batch: the length-aware instantiations (tap convs)
   if (bsel == 384) {
     if (kname) *kname = "conv_gemm_x3dw<384,128,halo>";
-    return sp ? launch_flat<384, 128>(conv_gemm_x3dw<64, true, 128>, p, batch, phases, 512, s)
-              : launch_flat<384, 128>(conv_gemm_x3dw<64, false, 128>, p, batch, phases, 512, s);
+    return p.clip_len ? launch_x3dw_halo<384, 128, true>(p, sp, batch, phases, s)
+                      : launch_x3dw_halo<384, 128, false>(p, sp, batch, phases, s);
   }
   if (p.taps == 1) {
     if (kname) *kname = "conv_gemm_x3dw<256,256>";
-    return sp ? launch_flat<256, 256>(conv_gemm_x3dw<0, true>, p, batch, phases, 512, s)
-              : launch_flat<256, 256>(conv_gemm_x3dw<0, false>, p, batch, phases, 512, s);
+    if (!sp) {
+      ++g_form_launches[kEpiFormCounters - 1];
+      return launch_flat<256, 256>(conv_gemm_x3dw<0, false>, p, batch, phases, 512, s);
+    }
+    return with_epi_form<EpiPw1, EpiPw2>(p, knobs(p).epi_generic, [&](auto f) {
+      return launch_flat<256, 256>(conv_gemm_x3dw<0, true, 256, false, decltype(f)>, p, batch, phases, 512, s);
+    });
   }
   if (kname) *kname = "conv_gemm_x3dw<256,256,halo>";
-  return sp ? launch_flat<256, 256>(conv_gemm_x3dw<64, true>, p, batch, phases, 512, s)
-            : launch_flat<256, 256>(conv_gemm_x3dw<64, false>, p, batch, phases, 512, s);
+  return p.clip_len ? launch_x3dw_halo<256, 256, true>(p, sp, batch, phases, s)
+                    : launch_x3dw_halo<256, 256, false>(p, sp, batch, phases, s);
+}
+
+template <int BN, bool RAG>
+static void launch_x3dw_group(const ConvGroup& g, bool split, unsigned blocks, hipStream_t s) {
+  if (!split) {
+    ++g_form_launches[kEpiFormCounters - 1];
+    hipLaunchKernelGGL((conv_gemm_x3dw_group<false, BN, RAG>), dim3(blocks), dim3(512), 0, s, g);
+    return;
+  }
+  (void)with_epi_form<EpiC1, EpiC2>(g.p[0], group_generic(g), [&](auto f) {  // (the caller reads hipGetLastError)
+    hipLaunchKernelGGL((conv_gemm_x3dw_group<true, BN, RAG, decltype(f)>), dim3(blocks), dim3(512), 0, s, g);
+    return hipSuccess;
+  });
 }
 
 // bsel 384 / 512: conv_gemm_x3dw_group; 256 / 128: conv_gemm_x3dq_group<bsel>
 hipError_t launch_h3_group(const ConvGroup& g, int bsel, bool split, unsigned blocks, hipStream_t s, const char** kname) {
-  if (g.p[0].clip_len) {  // ragged batch (every member of a group has the lengths or none): the length-aware instantiations
-    if (bsel == 384) {
-      if (kname) *kname = "conv_gemm_x3dw_group<384,128,halo>";
-      if (split) hipLaunchKernelGGL((conv_gemm_x3dw_group<true, 128, true>), dim3(blocks), dim3(512), 0, s, g);
-      else hipLaunchKernelGGL((conv_gemm_x3dw_group<false, 128, true>), dim3(blocks), dim3(512), 0, s, g);
-    } else if (bsel == 512) {
-      if (kname) *kname = "conv_gemm_x3dw_group<256,256,halo>";
-      if (split) hipLaunchKernelGGL((conv_gemm_x3dw_group<true, 256, true>), dim3(blocks), dim3(512), 0, s, g);
-      else hipLaunchKernelGGL((conv_gemm_x3dw_group<false, 256, true>), dim3(blocks), dim3(512), 0, s, g);
-    } else if (bsel == 256) {
-      if (kname) *kname = "conv_gemm_x3dq_group<128,256,halo>";
-      hipLaunchKernelGGL((conv_gemm_x3dq_group<256, true>), dim3(blocks), dim3(512), 0, s, g);
-    } else {
-      if (kname) *kname = "conv_gemm_x3dq_group<256,128,halo>";
-      hipLaunchKernelGGL((conv_gemm_x3dq_group<128, true>), dim3(blocks), dim3(512), 0, s, g);
-    }
-    return hipGetLastError();
-  }
+  const bool rag = g.p[0].clip_len != nullptr;  // ragged batch (every member of a group has the lengths or none): the length-aware instantiations
   if (bsel == 384) {
     if (kname) *kname = "conv_gemm_x3dw_group<384,128,halo>";
-    if (split) hipLaunchKernelGGL((conv_gemm_x3dw_group<true, 128>), dim3(blocks), dim3(512), 0, s, g);
-    else hipLaunchKernelGGL((conv_gemm_x3dw_group<false, 128>), dim3(blocks), dim3(512), 0, s, g);
+    if (rag) launch_x3dw_group<128, true>(g, split, blocks, s);
+    else launch_x3dw_group<128, false>(g, split, blocks, s);
   } else if (bsel == 512) {
     if (kname) *kname = "conv_gemm_x3dw_group<256,256,halo>";
-    if (split) hipLaunchKernelGGL(conv_gemm_x3dw_group<true>, dim3(blocks), dim3(512), 0, s, g);
-    else hipLaunchKernelGGL(conv_gemm_x3dw_group<false>, dim3(blocks), dim3(512), 0, s, g);
+    if (rag) launch_x3dw_group<256, true>(g, split, blocks, s);
+    else launch_x3dw_group<256, false>(g, split, blocks, s);
   } else if (bsel == 256) {
     if (kname) *kname = "conv_gemm_x3dq_group<128,256,halo>";
-    hipLaunchKernelGGL((conv_gemm_x3dq_group<256>), dim3(blocks), dim3(512), 0, s, g);
+    if (rag) hipLaunchKernelGGL((conv_gemm_x3dq_group<256, true>), dim3(blocks), dim3(512), 0, s, g);
+    else hipLaunchKernelGGL((conv_gemm_x3dq_group<256>), dim3(blocks), dim3(512), 0, s, g);
   } else {
     if (kname) *kname = "conv_gemm_x3dq_group<256,128,halo>";
-    hipLaunchKernelGGL((conv_gemm_x3dq_group<128>), dim3(blocks), dim3(512), 0, s, g);
+    if (rag) hipLaunchKernelGGL((conv_gemm_x3dq_group<128, true>), dim3(blocks), dim3(512), 0, s, g);
+    else hipLaunchKernelGGL((conv_gemm_x3dq_group<128>), dim3(blocks), dim3(512), 0, s, g);
   }
   return hipGetLastError();
 }

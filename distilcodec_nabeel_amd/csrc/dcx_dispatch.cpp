@@ -53,7 +53,8 @@ static const struct {
     {"DCX_SPLIT_GROUP_OFF", &dcx::Knobs::split_group_off}, {"DCX_H3", &dcx::Knobs::h3},
     {"DCX_H3_BN", &dcx::Knobs::h3_bn},                    {"DCX_H3_1X1", &dcx::Knobs::h3_1x1},
     {"DCX_H3_SPLIT", &dcx::Knobs::h3_split},              {"DCX_H3_PAIRS", &dcx::Knobs::h3_pairs},
-    {"DCX_RP_RING", &dcx::Knobs::rp_ring},                {"DCX_ENC_STREAMS", &dcx::Knobs::enc_streams}};
+    {"DCX_RP_RING", &dcx::Knobs::rp_ring},                {"DCX_ENC_STREAMS", &dcx::Knobs::enc_streams},
+    {"DCX_EPI_GENERIC", &dcx::Knobs::epi_generic},        {"DCX_CONV_GROUP", &dcx::Knobs::conv_group}};
 
 // the member a knob's name selects; null for unknown names
 int dcx::Knobs::*knob_slot(const std::string& n) {
@@ -367,7 +368,7 @@ int run_conv_group(dcx_codec* h, const ConvW* const* w, const ConvCall* c, int n
     const int rc = run_conv_group_split(h, w, c, p, n, fl, by, s);
     if (rc != 1) return rc;
   }
-  if (same && n > 1) {
+  if (same && n > 1 && h->knobs.conv_group) {
 #ifdef DCX_DIAG_DUP
     if (const int dm = diag_dup_mode()) {
       ConvParams q[dcx::kMaxGroup];

@@ -143,6 +143,8 @@ struct Knobs {
   int h3_pairs = 1;         // DCX_H3_PAIRS=0: the C = 32 / 64 ResBlock pairs in x6 arithmetic (A/B, tests)
   int h3_1x1 = 1;           // DCX_H3_1X1=0: the ConvNeXt blocks' 1x1 convs in x6 arithmetic (A/B, tests)
   int rp_ring = 1;          // DCX_RP_RING=0: conv_res_pair_h3's weights loaded per wave instead of the LDS ring (A/B)
+  int epi_generic = 0;      // DCX_EPI_GENERIC=1: the h3 convs' run-time epilogue instead of their compile-time forms (same bits; A/B, tests)
+  int conv_group = 1;       // DCX_CONV_GROUP=0: a stage's independent convs launched one by one instead of grouped (same bits; tests)
   int enc_streams = 2;      // DCX_ENC_STREAMS: half-batches on two streams, 0 off, 1 the encoder, 2 up to the generator, 3 the whole path (same bits)
 };
 
@@ -310,6 +312,10 @@ hipError_t launch_conv(const ConvParams& p, int batch, int phases, hipStream_t s
 // launches them one by one, which gives the same bits).
 hipError_t launch_conv_group(const ConvParams* ps, int n, int batch, hipStream_t s, const char** kname);
 hipError_t launch_res_pair(const ResPairParams& p, hipStream_t s, const char** kname);
+// Launches of the conv_gemm_x3dw kernels (single and grouped) so far in this process, by epilogue form
+// (dcx_conv_h3.hip: the nine forms in their order there, then the run-time epilogue), optionally reset.
+constexpr int kEpiFormCounters = 10;
+void epi_form_launches(long long* out, bool reset);
 // Split-K latency mode: the reduce kernel that sums `splits` fp32 partial outputs of a
 // ConvParams::ksplit launch (laid out like p.y, `stride` floats apart, in order) and applies p's
 // whole epilogue (bias, epi, mean, every output and layout).

@@ -25,7 +25,7 @@ KNOB_DEFAULTS = {
     "DCX_RP_R": 0, "DCX_RP_OLD": 0, "DCX_RP_G64": 0, "DCX_GELU_LUT": -1,
     "DCX_BF16_PERSIST": 1, "DCX_BF16_REG_EPI": 1, "DCX_DWCONV_TILED": 0, "DCX_SPLIT_MIN_STEPS": 0,
     "DCX_SPLIT_GROUP_OFF": 0, "DCX_H3": 1, "DCX_H3_BN": 0, "DCX_H3_1X1": 1, "DCX_H3_SPLIT": 1, "DCX_H3_PAIRS": 1, "DCX_RP_RING": 1,
-    "DCX_ENC_STREAMS": 2,
+    "DCX_ENC_STREAMS": 2, "DCX_EPI_GENERIC": 0, "DCX_CONV_GROUP": 1,
 }
 
 GEMM_MODES = {"f32": _native.DCX_GEMM_F32, "x6": _native.DCX_GEMM_X6, "bf16": _native.DCX_GEMM_BF16}
@@ -176,6 +176,13 @@ class NativeCodec:
         finally:
             for k, v in saved.items():
                 self.set_knob(k, v)
+
+    def epi_form_launches(self, reset: bool = False) -> list[int]:
+        """Launches of the wide h3 conv kernels in this process by epilogue form (dcx_epi_form_launches):
+        nine compile-time forms, then the run-time epilogue."""
+        v = (ctypes.c_int64 * 10)()
+        self._check(self.L.dcx_epi_form_launches(v, 10, int(reset)))
+        return list(v)
 
     def range_flags(self, reset: bool = False) -> int:
         """The h3 range flags (dcx_range_flags; synchronises): bit 0 a non-finite operand bound, bit 1
@@ -361,10 +368,15 @@ class NativeCodec:
         self._check(self.L.dcx_module_io(self.h, name.encode(), ctypes.byref(ci), ctypes.byref(co), ctypes.byref(r)))
         return ci.value, co.value, r.value
 
-    def module(self, name: str, x: torch.Tensor) -> torch.Tensor:
+    def module_workspace_size(self, name: str, batch: int, rows: int) -> int:
+        return int(self.L.dcx_module_workspace_size(self.h, name.encode(), batch, rows))
+
+    def module(self, name: str, x: torch.Tensor, ws: torch.Tensor | None = None) -> torch.Tensor:
         """One reference module by its state-dict prefix (dcx_module_forward): x channels-last
         (B, L, C) fp32 -> y (see the header for shapes; int32 codes for "quantizer.search").
-        ValueError for an unknown name or an input whose channel count is not the module's."""
+        ValueError for an unknown name or an input whose channel count is not the module's.
+        ws: a caller-owned workspace of at least module_workspace_size bytes (the module's intermediate
+        tensors, range maxima and shifts are laid out in it, in the same places for the same shapes)."""
         cin, cout, rate = self.module_io(name)
         x = self._dev(x, torch.float32)
         if x.ndim != 3 or x.shape[2] != cin:
@@ -378,7 +390,7 @@ class NativeCodec:
             y = torch.empty(B, L, dtype=torch.int32, device=self.device)
         else:
             y = torch.empty(B, L * rate, cout, device=self.device)
-        ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        ws = torch.empty(need, dtype=torch.uint8, device=self.device) if ws is None else self._workspace_of(need, ws)
         with torch.cuda.device(self.device):
             self._check(self.L.dcx_module_forward(self.h, n, self._ptr(x), B, L, C, self._ptr(y), self._ptr(ws), ws.numel(),
                                                   self._stream()))
@@ -477,3 +489,37 @@ class NativeConv:
         if rc != _native.DCX_OK:
             raise _native.NativeError(rc, "dcx_conv_forward failed")
         return (y, ys) if want_silu else y
+
+    def forward_h3(self, x: torch.Tensor, want_y: bool = False, want_silu: bool = False, want_silu_h2: bool = False,
+                   want_amax: bool = False, res: torch.Tensor | None = None, in_place: bool = False,
+                   macc: torch.Tensor | None = None, mean: int = 0, lens: torch.Tensor | None = None) -> dict:
+        """A tap conv in h3 arithmetic with the outputs a generator stage asks for (dcx_conv_forward_h3):
+        fp32 y / silu, the silu image in h2 (int16 words) with its per-clip shifts, the measured per-clip
+        max |v|; res: v = res + conv (in_place: y is res itself); mean 1 / 2 / 3 on macc (updated in
+        place); lens: int32 per-clip row counts.  Returns the requested tensors by name."""
+        B, L, C = x.shape
+        assert C == self.cin and x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and self.stride == 1
+        dev = x.device
+        out = {}
+        if want_y:
+            out["y"] = res if in_place else torch.empty(B, L, self.cout, device=dev)
+        if want_silu:
+            out["y_silu"] = torch.empty(B, L, self.cout, device=dev)
+        if want_silu_h2:
+            out["y_silu_h2"] = torch.zeros(B, L, self.cout * 2, dtype=torch.int16, device=dev)
+            out["y_ash"] = torch.zeros(B, dtype=torch.int32, device=dev)
+        if want_amax:
+            out["y_amax"] = torch.zeros(B, device=dev)
+        keep = [res.abs().amax(dim=(1, 2)).contiguous() if res is not None else None,
+                macc.abs().amax(dim=(1, 2)).contiguous() if macc is not None and mean >= 2 else None]
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        o = _native.ConvH3Out(ptr(out.get("y")), ptr(out.get("y_silu")), ptr(out.get("y_silu_h2")), ptr(out.get("y_ash")),
+                              ptr(out.get("y_amax")), ptr(res), ptr(keep[0]), ptr(macc), ptr(keep[1]), ptr(lens),
+                              3 if res is not None else 0, mean)
+        rc = self.L.dcx_conv_forward_h3(self.h, ctypes.c_void_p(x.data_ptr()), B, L, ctypes.byref(o),
+                                        ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc != _native.DCX_OK:
+            raise _native.NativeError(rc, "dcx_conv_forward_h3 failed")
+        if macc is not None:
+            out["macc"] = macc
+        return out

@@ -288,7 +288,9 @@ int dcx_set_split_k(dcx_codec* h, int32_t max_splits);
  * ResBlock pair kernel instead of its LDS ring); DCX_ENC_STREAMS (half-batches on the caller's stream
  * and a second stream, same bits: 0 none, 1 the encoder, 2 (default) dcx_encode_decode up to the
  * generator (mel, encoder, VQ encode / decode per half; the generator on the whole batch), 3 the
- * generator per half too)); no launch reads the environment.  This call changes
+ * generator per half too); DCX_EPI_GENERIC (1 = the h3 convs' run-time epilogue instead of their
+ * compile-time forms, same bits), DCX_CONV_GROUP (0 = a stage's independent convs launched one by
+ * one instead of as one grouped launch, same bits)); no launch reads the environment.  This call changes
  * one for later calls on this handle (a hipGraph captured earlier keeps the kernels it captured).
  * Unset, every switch selects the shipped path.  DCX_ERR_INVALID_ARG for an unknown name,
  * DCX_ERR_STATE during a stage call. */
@@ -327,6 +329,35 @@ void dcx_conv_destroy(dcx_conv* c);
  * exact range (one-tap: each row's), as the stages do for a caller's tensor.  Other convs and modes
  * are not affected.  Accuracy: the h3 contract of DCX_GEMM_X6 (2e-4 of the output's max). */
 const char* dcx_conv_last_kernel(const dcx_conv* c);
+/* dcx_conv_forward_h3: a tap conv (k >= 3 Conv1d) of the primitive in h3 arithmetic (dcx_conv_set_h3(c, 1),
+ * Cout % 128 == 0) with the outputs the generator's stages ask of such a conv, all device pointers, any
+ * of them NULL unless noted.  y, y_silu: v and silu(v) in fp32 [B][L][Cout]; y_silu_h2: silu(v) in the h2
+ * layout (4 bytes per element) scaled per clip by 2^y_ash[clip] (y_ash [B] required with it); y_amax [B]:
+ * receives max |v| per clip by an atomic maximum (zero it first).  epi 0 (bias) or 3 (v = res + conv,
+ * res may be y: in place; res_amax [B], max |res| per clip, is then required for the output's bound).
+ * mean 1 / 2 / 3: the ParallelBlock mean on macc [B][L][Cout]: first writes v, mid adds v, last forms
+ * (macc + v) / 3 as the value every other output is taken of (macc_amax [B], max |macc| per clip,
+ * required for mid and last).  lens [B] int32: per-clip row counts (ragged batch: rows at or beyond a
+ * length are written as zeros; x must be zero there).  DCX_ERR_INVALID_ARG where the conv is no h3 conv. */
+typedef struct dcx_conv_h3_out {
+  float* y;
+  float* y_silu;
+  uint16_t* y_silu_h2;
+  int32_t* y_ash;
+  float* y_amax;
+  const float* res;
+  const float* res_amax;
+  float* macc;
+  const float* macc_amax;
+  const int32_t* lens;
+  int32_t epi, mean;
+} dcx_conv_h3_out;
+int dcx_conv_forward_h3(dcx_conv* c, const float* x, int32_t batch, int64_t lin, const dcx_conv_h3_out* o, void* stream);
+/* Test hook: launches of the wide h3 conv kernels (conv_gemm_x3dw, single and grouped) in this process
+ * so far, by epilogue form: counts[0..8] the compile-time forms (c1, ConvT, c2, mean first / mid / last
+ * to h2 / last to fp32, pwconv1, pwconv2), counts[9] the run-time epilogue; n must be 10.  reset != 0
+ * zeroes them.  The kernel names (dcx_conv_last_kernel, the profile) are the same for every form. */
+int dcx_epi_form_launches(int64_t* counts, int32_t n, int32_t reset);
 int dcx_conv_set_knob(dcx_conv* c, const char* name, int32_t value);
 int dcx_conv_set_h3(dcx_conv* c, int32_t on);
 
