@@ -467,6 +467,18 @@ class DistilCodec:
             wav = eng.decode_ragged(torch.from_numpy(codes), lengths)
         return [wav[b: b + 1, None, : eng.hop * int(n)].detach() for b, n in enumerate(lengths)]
 
+    def token_stream(self, sessions: int, push_frames: int, halo_frames: int = None, graph: bool = True):
+        """Opt-in, not in the reference: a `streaming.TokenStream` on this codec's engine, for `sessions`
+        utterances whose LLM token ids arrive a few frames at a time.  `push_tokens(ids_per_slot,
+        final=..., restart=...)` takes the flat frame-major ids `encode` yields (`token_id_offset`
+        subtracted as in `decode_from_codes`) and returns, per slot, the (1, 1, n) samples that became
+        final; a slot's outputs together are `decode_from_codes` of its whole list up to fp32
+        summation order.  fp32 only (the bf16 kernels do not take per-clip lengths)."""
+        from .streaming import TokenStream
+
+        return TokenStream(self._engine(), sessions, push_frames, halo_frames, graph=graph,
+                           token_id_offset=self.tokens_id_offset)
+
     def forward(self, audio_pathes: list):
         """distil_codec.py:518-530 (eval semantics)."""
         audios, mel_specs, gen_time_lengths, n_hop_lengths = self.preprocess_audio_batch(audio_pathes=audio_pathes)

@@ -1,6 +1,7 @@
 // The C ABI of include/distilcodec_amd.h over the host runtime (dcx_host.h): handles, the stage and
 // ragged exports, knobs, range flags, the dcx_conv primitive and the profile exports.
 #include "dcx_host.h"
+#include "dcx_stream_plan.h"
 
 namespace {
 
@@ -402,6 +403,76 @@ int dcx_decode_ragged(dcx_codec* h, const int32_t* codes, const int32_t* lengths
   STAGE_PRE(true);
   RUN(ragged_decode_pre(h, codes, lengths_dev, frames_max, wav));
   return stage_decode_ragged(h, codes, lengths_dev, batch, (int)frames_max, wav, n_invalid, ws, s);
+}
+
+// Token streams: the geometry every entry takes, and the views of the caller's state
+// buffer for it (false: refused, with the reason in dcx_last_error).
+static bool stream_geometry(const dcx_codec* h, int32_t sessions, int32_t push, int32_t halo) {
+  return h && sessions >= 1 && sessions <= dcx::kStreamMaxSessions && push >= 1 && push <= dcx::kStreamMaxFrames &&
+         halo >= 0 && halo <= dcx::kStreamMaxFrames;
+}
+
+static int stream_state(dcx_codec* h, void* state, size_t state_bytes, int32_t sessions, int32_t push, int32_t halo,
+                        dcx::StreamState& st) {
+  if (!stream_geometry(h, sessions, push, halo))
+    return fail(h, DCX_ERR_INVALID_ARG, "token stream: sessions must be in [1, 65535], push_frames in [1, 65536], halo_frames in [0, 65536]");
+  if (!state || (reinterpret_cast<uintptr_t>(state) & 15))
+    return fail(h, DCX_ERR_INVALID_ARG, "token stream: null or misaligned state buffer (16 bytes)");
+  const size_t need = dcx::stream_state_layout(state, sessions, push, halo, h->n_layers, h->cfg.hop, st);
+  if (state_bytes < need)
+    return fail(h, DCX_ERR_INVALID_ARG, "token stream: the state buffer holds " + std::to_string(state_bytes) + " bytes, " +
+                                            std::to_string(need) + " needed (dcx_stream_state_size)");
+  return DCX_OK;
+}
+
+size_t dcx_stream_state_size(const dcx_codec* h, int32_t sessions, int32_t push_frames, int32_t halo_frames) {
+  if (!stream_geometry(h, sessions, push_frames, halo_frames)) return 0;
+  dcx::StreamState st{};
+  return dcx::stream_state_layout(nullptr, sessions, push_frames, halo_frames, h->n_layers, h->cfg.hop, st);
+}
+
+int dcx_stream_plan_step(int32_t halo_frames, int32_t push_frames, int32_t* T, int32_t* E, int32_t* closed, int32_t n_new,
+                         int32_t flags, int32_t* len, int32_t* skip, int32_t* take) {
+  if (halo_frames < 0 || push_frames < 1 || !T || !E || !closed) return DCX_ERR_INVALID_ARG;
+  dcx::StreamSlot s{*T, *E, *closed};
+  const dcx::StreamStep o = dcx::stream_plan_step(halo_frames, push_frames, s, n_new, flags);
+  *T = s.T;
+  *E = s.E;
+  *closed = s.closed;
+  if (len) *len = o.len;
+  if (skip) *skip = o.skip;
+  if (take) *take = o.take;
+  return DCX_OK;
+}
+
+int dcx_stream_reset(dcx_codec* h, void* state, size_t state_bytes, int32_t sessions, int32_t push_frames,
+                     int32_t halo_frames, void* stream) {
+  if (!h) return DCX_ERR_INVALID_ARG;
+  dcx::StreamState st{};
+  RUN(stream_state(h, state, state_bytes, sessions, push_frames, halo_frames, st));
+  RUN(check_ready(h, false));
+  HIPCHK(h, dcx::launch_stream_reset(st, (hipStream_t)stream));
+  return DCX_OK;
+}
+
+int dcx_stream_decode_step(dcx_codec* h, void* state, size_t state_bytes, int32_t sessions, int32_t push_frames,
+                           int32_t halo_frames, const int32_t* new_codes, const int32_t* n_new_dev,
+                           const int32_t* flags_dev, float* wav_out, int32_t* n_out_dev, int32_t* n_invalid,
+                           void* workspace, size_t ws_bytes, void* stream) {
+  if (!h) return DCX_ERR_INVALID_ARG;
+  dcx::StreamState st{};
+  RUN(stream_state(h, state, state_bytes, sessions, push_frames, halo_frames, st));
+  if (!new_codes || !n_new_dev || !flags_dev || !wav_out || !n_out_dev || (reinterpret_cast<uintptr_t>(wav_out) & 15))
+    return fail(h, DCX_ERR_INVALID_ARG, "token stream: null buffer, or wav_out not on a 16-byte boundary");
+  const int32_t batch = sessions;
+  STAGE_PRE(true);
+  RUN(ragged_decode_pre(h, new_codes, st.len, st.W, wav_out));
+  // what the decode would refuse after the plan kernel has run is refused here, before any launch
+  Bump dry(nullptr, 0, true);
+  RUN(stage_decode_ragged(h, nullptr, nullptr, batch, st.W, nullptr, nullptr, dry, s));
+  if (ws_bytes < dry.off)
+    return fail(h, DCX_ERR_INVALID_ARG, "token stream: workspace too small (dcx_workspace_size(h, sessions, push_frames + 2 halo_frames))");
+  return stage_stream_step(h, st, new_codes, n_new_dev, flags_dev, wav_out, n_out_dev, n_invalid, ws, s);
 }
 
 int dcx_module_io(const dcx_codec* h, const char* module, int32_t* in_channels, int32_t* out_channels,

@@ -455,6 +455,9 @@ int stage_encode_decode(dcx_codec* h, const float* audio, int B, int64_t n, int3
                         hipStream_t s);
 int stage_decode_ragged(dcx_codec* h, const int32_t* codes, const int* lens, int B, int T, float* wav,
                         int32_t* n_invalid, Bump& ws, hipStream_t s);
+// one step of a token stream on the state st views: n_invalid counts the codes the step appends
+int stage_stream_step(dcx_codec* h, const dcx::StreamState& st, const int32_t* new_codes, const int* n_new,
+                      const int* flags, float* wav_out, int* n_out, int32_t* n_invalid, Bump& ws, hipStream_t s);
 
 // ---- dcx_generator.cpp ----
 bool h3_stage(const dcx_codec* h, int i, long long rows);

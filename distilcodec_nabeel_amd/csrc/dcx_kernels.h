@@ -500,6 +500,55 @@ hipError_t launch_zero_tail_rows(float* x, int batch, long long L, int C, const 
 // read as zeros and the samples there are written as zeros (a block wholly beyond it computes nothing)
 hipError_t launch_conv_post_tanh(const float* x, const float* w, float bias, float* out, int batch, int L, int C,
                                  int k, int bf16, hipStream_t s, const int* clip_len = nullptr, int len_mul = 1);
+// ---- token streams (dcx_stream.hip; DESIGN.md §3 "Token streams") ----
+// The caller's state buffer of `sessions` slots, push size P, halo h, W = P + 2 h window frames, R codes
+// per frame: eleven [sessions] int arrays (the counters of dcx_stream_plan.h; the counters a step
+// leaves, committed by the emit kernel once every launch before it was accepted; the step's outputs),
+// the code ring [sessions][W][R] (frame f at row f % W), the step's window [sessions][W][R] and its
+// waveform [sessions][W * hop], each part on a 256-byte boundary.
+struct StreamState {
+  int *T, *E, *closed;           // the slots' counters
+  int *T_next, *E_next, *closed_next;
+  int *len, *skip, *take, *t_old, *n;  // the step's outputs
+  int32_t *ring, *window;
+  float* wav;
+  int sessions, push, halo, W, R, hop;
+};
+constexpr int kStreamCounters = 11;
+constexpr int kStreamMaxSessions = 65535, kStreamMaxFrames = 1 << 16;  // grid.y; push and halo each
+// the views of a state buffer at `base` (may be null: sizing) and its size in bytes
+inline size_t stream_state_layout(void* base, int sessions, int push, int halo, int R, int hop, StreamState& st) {
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t B = (size_t)sessions, W = (size_t)push + 2 * (size_t)halo;
+  char* p = (char*)base;
+  size_t off = 0;
+  int** ctr[kStreamCounters] = {&st.T, &st.E, &st.closed, &st.T_next, &st.E_next, &st.closed_next,
+                                &st.len, &st.skip, &st.take, &st.t_old, &st.n};
+  for (int i = 0; i < kStreamCounters; ++i) *ctr[i] = (int*)(p + off + i * B * sizeof(int));
+  off = up(off + kStreamCounters * B * sizeof(int));
+  st.ring = (int32_t*)(p + off);
+  off = up(off + B * W * R * sizeof(int32_t));
+  st.window = (int32_t*)(p + off);
+  off = up(off + B * W * R * sizeof(int32_t));
+  st.wav = (float*)(p + off);
+  off = up(off + B * W * hop * sizeof(float));
+  st.sessions = sessions; st.push = push; st.halo = halo; st.W = (int)W; st.R = R; st.hop = hop;
+  return off;
+}
+// every slot empty (the counters zeroed; the ring is only read where a step wrote it)
+hipError_t launch_stream_reset(const StreamState& st, hipStream_t s);
+// one thread per slot: stream_plan_step on the slot's counters with n_new[b] / flags[b] (device), the
+// step's outputs and the counters it leaves written to the state
+hipError_t launch_stream_plan(const StreamState& st, const int* n_new, const int* flags, hipStream_t s);
+// window[b][j] = code frame T - len + j for j < len (zeros beyond), from the ring or, for the frames this
+// step appends, from new_codes [sessions][push][R], which are stored into the ring too; n_invalid (may be
+// null) counts the appended codes outside the codebook by launch_gather_rows' rule
+hipError_t launch_stream_window(const StreamState& st, const int32_t* new_codes, int ncodes, int32_t* n_invalid,
+                                hipStream_t s);
+// out[b] = the window waveform's frames [skip, skip + take), then zeros up to (push + halo) * hop samples;
+// n_out[b] = take; the slot's counters take the values the plan kernel left
+hipError_t launch_stream_emit(const StreamState& st, float* out, int* n_out, hipStream_t s);
+
 hipError_t launch_transpose(const float* in, float* out, int batch, long long rows, long long cols, hipStream_t s);
 hipError_t launch_resample_poly(const float* x, int batch, long long n_in, long long xs, const double* h, int hlen,
                                 int up, int down, long long pre, float* y, long long n_out, long long ys,

@@ -533,6 +533,22 @@ int stage_decode_ragged(dcx_codec* h, const int32_t* codes, const int* lens, int
   return stage_generate(h, CAct(z), B, T, wav, tail, s, lens);
 }
 
+// One step of a token stream (dcx_stream_decode_step): the slots' plan, their windows of codes, the
+// ragged decode of the windows as dcx_decode_ragged runs it for (sessions, W), and the emitted frames.
+// The emit kernel commits the slots' counters, so a step that fails before it leaves the state as it was.
+int stage_stream_step(dcx_codec* h, const dcx::StreamState& st, const int32_t* new_codes, const int* n_new,
+                      const int* flags, float* wav_out, int* n_out, int32_t* n_invalid, Bump& ws, hipStream_t s) {
+  const double codes = (double)st.sessions * st.W * st.R;
+  LAUNCH(h, s, "stream_plan", 0, 4.0 * dcx::kStreamCounters * st.sessions, dcx::launch_stream_plan(st, n_new, flags, s));
+  LAUNCH(h, s, "stream_window", 0, 8.0 * codes, dcx::launch_stream_window(st, new_codes, h->cfg.codebook_size, n_invalid, s));
+  // the appended codes were counted once, as they arrived: the decode would count a bad code again in
+  // every window that holds it
+  RUN(stage_decode_ragged(h, st.window, st.len, st.sessions, st.W, st.wav, nullptr, ws, s));
+  LAUNCH(h, s, "stream_emit", 0, 8.0 * st.sessions * (st.push + st.halo) * st.hop,
+         dcx::launch_stream_emit(st, wav_out, n_out, s));
+  return DCX_OK;
+}
+
 // Half-batches on two streams (Knobs::enc_streams >= 2; 1 forks inside the encoder only): clips
 // [0, B0) on the caller's stream and [B0, B) on the side stream, each in its own part of the
 // workspace (half 0's, then half 1's: the sizes are linear in the clip count).  Every stage computes

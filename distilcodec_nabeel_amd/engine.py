@@ -362,6 +362,65 @@ class NativeCodec:
                                                  self._ptr(n_invalid), self._ptr(ws), ws.numel(), self._stream()))
         return wav
 
+    # ------------------------------------------------------------------ token streams
+    # Thin wrappers of dcx_stream_*: every tensor is the caller's, so a captured hipGraph keeps its
+    # buffers (streaming.TokenStream owns them and mirrors the slots' counters on the host).
+    def stream_state_size(self, sessions: int, push_frames: int, halo_frames: int) -> int:
+        return int(self.L.dcx_stream_state_size(self.h, sessions, push_frames, halo_frames))
+
+    def stream_state(self, sessions: int, push_frames: int, halo_frames: int) -> torch.Tensor:
+        """A reset state buffer for `sessions` slots (dcx_stream_state_size, dcx_stream_reset)."""
+        need = self.stream_state_size(sessions, push_frames, halo_frames)
+        if need == 0:
+            raise ValueError(f"token stream: bad geometry (sessions={sessions}, push_frames={push_frames}, "
+                             f"halo_frames={halo_frames})")
+        state = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self.stream_reset(state, sessions, push_frames, halo_frames)
+        return state
+
+    def stream_reset(self, state: torch.Tensor, sessions: int, push_frames: int, halo_frames: int) -> None:
+        with torch.cuda.device(self.device):
+            self._check(self.L.dcx_stream_reset(self.h, self._ptr(state), state.numel(), sessions, push_frames, halo_frames,
+                                                self._stream()))
+
+    def stream_step(self, state: torch.Tensor, sessions: int, push_frames: int, halo_frames: int, new_codes: torch.Tensor,
+                    n_new: torch.Tensor, flags: torch.Tensor, wav_out: torch.Tensor, n_out: torch.Tensor,
+                    n_invalid: torch.Tensor | None = None, ws: torch.Tensor | None = None) -> None:
+        """One step of every slot (dcx_stream_decode_step) on the caller's device tensors: new_codes
+        int32 (sessions, push_frames(, R)), n_new / flags / n_out int32 (sessions,), wav_out fp32
+        (sessions, 256 (push_frames + halo_frames)), n_invalid int32 (1,) or None."""
+        if not self.with_generator:
+            raise RuntimeError("this engine was built without generator weights")
+        B, P, h = sessions, push_frames, halo_frames
+        want = {"new_codes": (new_codes, torch.int32, self._codes_shape(B, P)), "n_new": (n_new, torch.int32, (B,)),
+                "flags": (flags, torch.int32, (B,)), "n_out": (n_out, torch.int32, (B,)),
+                "wav_out": (wav_out, torch.float32, (B, self.hop * (P + h)))}
+        if n_invalid is not None:
+            want["n_invalid"] = (n_invalid, torch.int32, (1,))
+        for name, (t, dtype, shape) in want.items():
+            if t.device != self.device or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {dtype} tensor shaped {shape} on {self.device}")
+        if ws is None:
+            ws = self.workspace(B, P + 2 * h)
+        elif ws.device != self.device or ws.dtype != torch.uint8 or not ws.is_contiguous():
+            raise ValueError(f"workspace must be a contiguous uint8 tensor on {self.device}")
+        with torch.cuda.device(self.device):  # the call itself checks the sizes of state and ws
+            self._check(self.L.dcx_stream_decode_step(self.h, self._ptr(state), state.numel(), B, P, h, self._ptr(new_codes),
+                                                      self._ptr(n_new), self._ptr(flags), self._ptr(wav_out),
+                                                      self._ptr(n_out), self._ptr(n_invalid), self._ptr(ws), ws.numel(),
+                                                      self._stream()))
+
+    @staticmethod
+    def stream_plan_step(halo_frames: int, push_frames: int, T: int, E: int, closed: int, n_new: int, flags: int):
+        """dcx_stream_plan_step (host only): (T, E, closed, len, skip, take) after one step of a slot."""
+        L = _native.lib()
+        v = [ctypes.c_int32(x) for x in (T, E, closed, 0, 0, 0)]
+        rc = L.dcx_stream_plan_step(halo_frames, push_frames, ctypes.byref(v[0]), ctypes.byref(v[1]), ctypes.byref(v[2]),
+                                    n_new, flags, ctypes.byref(v[3]), ctypes.byref(v[4]), ctypes.byref(v[5]))
+        if rc != _native.DCX_OK:
+            raise ValueError("dcx_stream_plan_step: halo_frames must be >= 0 and push_frames >= 1")
+        return tuple(x.value for x in v)
+
     def module_io(self, name: str) -> tuple[int, int, int]:
         """(input channels, output channels (0: int32 codes), output rows per input row) of a module."""
         ci, co, r = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()

@@ -5,6 +5,8 @@ output samples), B = 1, one hipGraph-captured step, p50/p99 latency. Each hop is
 decoded on its own, exactly as the reference does for a 1 s clip
 (`DistilCodec.encode` + `decode_from_codes`, distil_codec.py:545-594). `HaloStream` below is the
 halo-overlapped variant whose chunked output equals the full-clip output.
+`TokenStream` is the other direction for many sessions at once: codes -> audio while the codes are
+still arriving, one dcx_stream_decode_step per push (DESIGN.md §3 "Token streams").
 
 The C-ABI stage calls allocate nothing and never synchronise (include/distilcodec_amd.h), so a
 whole `dcx_encode_decode` call is captured by `torch.cuda.graph` as it is launched: every kernel
@@ -83,6 +85,145 @@ def receptive_field(cfg: dict) -> tuple[int, int]:
         d += res / rate
     d += dec.get("post_conv_kernel_size", 13) // 2 / hop
     return int(e), int(math.ceil(d))
+
+
+class TokenStream:
+    """Batched streaming decode, codes -> audio (DESIGN.md §3 "Token streams"): `sessions` utterances
+    that each grow by at most `push_frames` frames per `push`, decoded together in one
+    dcx_stream_decode_step per push, every slot's samples those of its full-clip decode up to fp32
+    summation order.  A frame's audio is returned once `halo_frames` codes after it have arrived
+    (default: the decoder's half receptive field, `receptive_field(cfg)[1]`), or when the slot is
+    marked `final`; the slot's state lives on the device, and the slots' counters are mirrored on the
+    host (dcx_stream_plan_step), so `push` reads nothing back and never synchronises.
+
+    `graph=True` captures the step once in a HIP graph over the stream's static tensors and replays
+    it per push, bit-equal to the eager step.  `n_invalid` (device int32 [1]) counts pushed codes
+    outside the codebook; it stays 0 after the host-side validation `push` does.
+    """
+
+    FINAL, RESTART = 1, 2
+    UNUSED = 1 << 20  # fills the entries of new_codes beyond a slot's count: never read
+
+    def __init__(self, engine: NativeCodec, sessions: int, push_frames: int, halo_frames: int | None = None,
+                 graph: bool = False, token_id_offset: int = 0):
+        self.engine = engine
+        self.sessions, self.push_frames = int(sessions), int(push_frames)
+        self.halo_frames = receptive_field(engine.cfg)[1] if halo_frames is None else int(halo_frames)
+        self.token_id_offset = token_id_offset
+        B, P, h, R, dev = self.sessions, self.push_frames, self.halo_frames, engine.R, engine.device
+        self.state = engine.stream_state(B, P, h)  # ValueError for a bad geometry
+        # the step's inputs as views of one buffer, uploaded in one copy from pinned memory
+        n_codes = B * P * R
+        self._in = torch.zeros(n_codes + 2 * B, dtype=torch.int32, device=dev)
+        # (a few host buffers in turn, each reused once its own upload has run: push does not wait for the device)
+        self._hosts = [torch.zeros(n_codes + 2 * B, dtype=torch.int32).pin_memory() for _ in range(4)]
+        self._uploaded = [None] * len(self._hosts)
+        self._turn = 0
+        self.new_codes = self._in[:n_codes].view(engine._codes_shape(B, P))
+        self.n_new, self.flags = self._in[n_codes:n_codes + B], self._in[n_codes + B:]
+        self.wav_out = torch.zeros(B, engine.hop * (P + h), device=dev)
+        self.n_out = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.n_invalid = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.ws = torch.empty(engine.workspace_size(B, P + 2 * h), dtype=torch.uint8, device=dev)
+        self._slots = [(0, 0, 0)] * B  # host mirror of (T, E, closed)
+        self.graph = None
+        if graph:
+            with torch.cuda.device(dev):
+                s = torch.cuda.Stream(dev)  # eager warm-up (first-launch work) off the capture
+                s.wait_stream(torch.cuda.current_stream(dev))
+                with torch.cuda.stream(s):
+                    self._step()  # every slot pushes nothing: the counters stay 0
+                    engine.stream_reset(self.state, B, P, h)
+                torch.cuda.current_stream(dev).wait_stream(s)
+                self.graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(self.graph):
+                    self._step()
+
+    def _step(self):
+        self.engine.stream_step(self.state, self.sessions, self.push_frames, self.halo_frames, self.new_codes, self.n_new,
+                                self.flags, self.wav_out, self.n_out, self.n_invalid, ws=self.ws)
+
+    def slot(self, b: int) -> tuple[int, int, bool]:
+        """(codes received, frames emitted, closed) of slot b, from the host mirror."""
+        T, E, closed = self._slots[b]
+        return T, E, bool(closed)
+
+    def push(self, codes_per_slot, final=(), restart=()) -> list:
+        """One step.  `codes_per_slot`: per slot, None or the new frames' codes, [n] ([n, R] for R > 1
+        codebooks), n <= push_frames; `final` / `restart`: the slots that end with this push / start
+        a new utterance with it.  Returns one 1-D tensor of the 256 take samples that became final per
+        slot.  ValueError for too many frames or a wrong shape, RuntimeError for codes pushed to a
+        closed slot without `restart`, IndexError for a code outside the codebook: all before any
+        upload, so a refused push changes nothing."""
+        import numpy as np
+
+        eng, B, P, R = self.engine, self.sessions, self.push_frames, self.engine.R
+        if len(codes_per_slot) != B:
+            raise ValueError(f"expected one entry per slot ({B}), got {len(codes_per_slot)}")
+        final, restart = set(final), set(restart)
+        if not (final | restart) <= set(range(B)):
+            raise ValueError(f"final / restart name slots outside [0, {B})")
+        stage = np.full((B, P, R), self.UNUSED, dtype=np.int32)
+        counts, flags = [0] * B, [0] * B
+        for b, c in enumerate(codes_per_slot):
+            flags[b] = (self.FINAL if b in final else 0) | (self.RESTART if b in restart else 0)
+            if c is None:
+                continue
+            c = np.asarray(c.cpu() if isinstance(c, torch.Tensor) else c)
+            if c.ndim == 1 and R == 1:
+                c = c[:, None]
+            if c.ndim != 2 or c.shape[1] != R:
+                raise ValueError(f"slot {b}: codes must be shaped {eng._codes_shape('n')}, got {tuple(c.shape)}")
+            n = c.shape[0]
+            if n > P:
+                raise ValueError(f"slot {b}: {n} frames exceed push_frames={P}")
+            if n and self._slots[b][2] and b not in restart:
+                raise RuntimeError(f"slot {b} is closed: pass it in `restart` to start a new utterance")
+            if n and (int(c.min()) < 0 or int(c.max()) >= eng.NC):
+                raise IndexError(f"slot {b}: audio code out of range for a codebook of {eng.NC} entries")
+            stage[b, :n] = c
+            counts[b] = n
+        k = self._turn
+        self._turn = (k + 1) % len(self._hosts)
+        if self._uploaded[k] is not None:
+            self._uploaded[k].synchronize()  # the upload of four pushes ago
+        host = self._hosts[k].numpy()
+        host[:B * P * R] = stage.reshape(-1)
+        host[B * P * R:B * P * R + B] = counts
+        host[B * P * R + B:] = flags
+        with torch.cuda.device(eng.device):
+            self._in.copy_(self._hosts[k], non_blocking=True)
+            self._uploaded[k] = torch.cuda.Event()
+            self._uploaded[k].record()
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            self._step()
+        out = self.wav_out.clone()  # the static output is overwritten by the next push
+        outs = []
+        for b in range(B):
+            T, E, closed, _, _, take = eng.stream_plan_step(self.halo_frames, P, *self._slots[b], counts[b], flags[b])
+            self._slots[b] = (T, E, closed)
+            outs.append(out[b, :eng.hop * take])
+        return outs
+
+    def push_tokens(self, token_ids_per_slot, final=(), restart=(), minus_token_offset: bool = True) -> list:
+        """`push` for the flat frame-major LLM token ids `DistilCodec.encode` yields (R ids per frame;
+        ValueError for a list that is not a multiple of R), `token_id_offset` subtracted as
+        `decode_from_codes` does.  Returns one (1, 1, n) tensor per slot."""
+        import numpy as np
+
+        R, off = self.engine.R, self.token_id_offset if minus_token_offset else 0
+        codes = []
+        for b, ids in enumerate(token_ids_per_slot):
+            if ids is None:
+                codes.append(None)
+                continue
+            a = np.asarray(ids, dtype=np.int64).reshape(-1)
+            if a.size % R:
+                raise ValueError(f"slot {b}: a code list of {a.size} entries is not a multiple of the {R} codebooks per frame")
+            codes.append((a - off).reshape(-1, R))
+        return [w[None, None, :] for w in self.push(codes, final=final, restart=restart)]
 
 
 class HaloStream:

@@ -210,6 +210,48 @@ int dcx_decode_ragged(dcx_codec* h, const int32_t* codes, const int32_t* lengths
                       int64_t frames_max, float* wav, int32_t* n_invalid, void* workspace, size_t ws_bytes,
                       void* stream);
 
+/* Token streams: batched streaming decode, codes -> audio, for `sessions` utterances that each grow by
+ * at most push_frames frames (of R codes, frame-major) per step.  Every step returns the samples that
+ * became final, and an utterance's samples together are those of its full-clip decode up to fp32
+ * summation order (a frame is final once halo_frames codes after it have arrived, or at FINAL; the
+ * decoder's receptive field is 21 frames for the published model).
+ * A slot holds T (codes received), E (frames emitted), closed, and the codes of frames [max(0, E - h), T).
+ * One step, per slot b, with n = n_new_dev[b] clamped to [0, push_frames] and flags_dev[b]:
+ *   1. DCX_STREAM_RESTART: T = E = 0, closed = 0.       2. closed: n = 0 (the new codes are ignored).
+ *   3. T += n; g0 = max(0, E - h); f_new = FINAL ? T : max(E, T - h).
+ *   4. the window is codes [g0, T), len = T - g0 <= W = push_frames + 2 h; it is decoded as
+ *      dcx_decode_ragged decodes a batch [sessions][W] with lengths len, so an utterance's true start and
+ *      its true end (at FINAL) see the zero padding of the full clip.
+ *   5. frames [E, f_new) are emitted: window rows [E - g0, f_new - g0), take = f_new - E frames
+ *      (<= push_frames, <= push_frames + h at FINAL).      6. E = f_new; FINAL sets closed.
+ *   wav_out[b][0 : 256 take)                               the emitted samples;
+ *   wav_out[b][256 take : 256 (push_frames + h))           written as 0;      n_out_dev[b] = take.
+ * new_codes [sessions][push_frames][R], n_new_dev, flags_dev, n_out_dev [sessions] and wav_out
+ * [sessions][256 (push_frames + h)] (on a 16-byte boundary) are DEVICE memory, so one hipGraph captured
+ * for a geometry serves every step.  Entries of new_codes at or beyond n are never read.  *n_invalid
+ * (device int, may be NULL, never reset here) counts each appended code outside the codebook once.
+ * All state lives in the caller's device buffer `state` (16-byte aligned, dcx_stream_state_size bytes;
+ * 0 for bad arguments), which dcx_stream_reset empties; workspace: dcx_workspace_size(h, sessions,
+ * push_frames + 2 h).  Every call takes the same (sessions, push_frames, halo_frames).  Stream-ordered,
+ * allocates nothing, never synchronises, capturable.  The slots' counters are committed by the step's
+ * last kernel: a step that returns an error leaves every slot as it was.
+ * dcx_stream_plan_step (host only, no HIP call, no handle): the same arithmetic on one slot's counters,
+ * so a caller mirrors T / E / closed and knows every take without reading device memory back.
+ * DCX_ERR_INVALID_ARG: sessions < 1 (> 65535), push_frames < 1, halo_frames < 0 (each > 65536), a null
+ * or short state buffer, a short workspace; and whatever dcx_decode_ragged refuses, with its status and
+ * reason (another gemm mode, DCX_H3=0, DCX_H3_PAIRS=0: DCX_ERR_INVALID_ARG; split-K: DCX_ERR_STATE). */
+#define DCX_STREAM_FINAL 1
+#define DCX_STREAM_RESTART 2
+size_t dcx_stream_state_size(const dcx_codec* h, int32_t sessions, int32_t push_frames, int32_t halo_frames);
+int dcx_stream_reset(dcx_codec* h, void* state, size_t state_bytes, int32_t sessions, int32_t push_frames,
+                     int32_t halo_frames, void* stream);
+int dcx_stream_decode_step(dcx_codec* h, void* state, size_t state_bytes, int32_t sessions, int32_t push_frames,
+                           int32_t halo_frames, const int32_t* new_codes, const int32_t* n_new_dev,
+                           const int32_t* flags_dev, float* wav_out, int32_t* n_out_dev, int32_t* n_invalid,
+                           void* workspace, size_t ws_bytes, void* stream);
+int dcx_stream_plan_step(int32_t halo_frames, int32_t push_frames, int32_t* T, int32_t* E, int32_t* closed,
+                         int32_t n_new, int32_t flags, int32_t* len, int32_t* skip, int32_t* take);
+
 /* Sample-rate conversion by up/down for input audio at another rate (replaces librosa.resample,
  * distil_codec.py:108-110 and :676, and librosa.load(sr=...) in meldataset.py:18-20).  Polyphase FIR
  * in scipy.signal.resample_poly's form: y[b][i] = sum_m h[(i + pre)*down - up*m] * x[b][m] over the
