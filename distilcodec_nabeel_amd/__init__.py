@@ -12,7 +12,7 @@ from .codec import (  # noqa: F401
     load_and_resample_audio,
 )
 from .config import default_config, load_config  # noqa: F401
-from .streaming import HaloStream, TokenStream, receptive_field  # noqa: F401
+from .streaming import AudioStream, HaloStream, TokenStream, receptive_field  # noqa: F401
 
 __all__ = ["DistilCodec", "GRVQResult", "decode_audio", "demo_for_generate_audio_codes", "load_and_resample_audio",
-           "default_config", "load_config", "HaloStream", "TokenStream", "receptive_field"]
+           "default_config", "load_config", "HaloStream", "TokenStream", "AudioStream", "receptive_field"]

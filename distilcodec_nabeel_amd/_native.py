@@ -102,6 +102,15 @@ SIGNATURES = {
     "dcx_stream_decode_step": (ctypes.c_int, [_P, _P, _SZ, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
     "dcx_stream_plan_step": (ctypes.c_int, [_I32, _I32, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I32),
                                             _I32, _I32, ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
+    "dcx_tokenize_slots": (ctypes.c_int, [_P, _P, _P, _I32, _I64, _P, _P, _P, _SZ, _P]),
+    "dcx_stream_encode_state_size": (_SZ, [_P, _I32, _I32, _I32, _I32]),
+    "dcx_stream_encode_geometry": (ctypes.c_int, [_P, _I32, _I32, ctypes.POINTER(_I64), ctypes.POINTER(_I64),
+                                                  ctypes.POINTER(_I64)]),
+    "dcx_stream_encode_reset": (ctypes.c_int, [_P, _P, _SZ, _I32, _I32, _I32, _I32, _P]),
+    "dcx_stream_encode_step": (ctypes.c_int, [_P, _P, _SZ, _I32, _I32, _I32, _P, _P, _P, _P, _P, _P, _P, _SZ, _P]),
+    "dcx_stream_encode_plan_step": (ctypes.c_int, [_P, _I32, _I32, ctypes.POINTER(_I32), ctypes.POINTER(_I32),
+                                                   ctypes.POINTER(_I32), _I32, _I32, ctypes.POINTER(_I32),
+                                                   ctypes.POINTER(_I32), ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
     "dcx_transpose": (ctypes.c_int, [_P, _P, _I32, _I64, _I64, _P]),
     "dcx_mp3_info": (ctypes.c_int, [_P, _SZ, ctypes.POINTER(_I64), ctypes.POINTER(_I32), ctypes.POINTER(_I32)]),
     "dcx_mp3_decode": (ctypes.c_int, [_P, _SZ, _P, _I64]),

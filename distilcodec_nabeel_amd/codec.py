@@ -479,6 +479,21 @@ class DistilCodec:
         return TokenStream(self._engine(), sessions, push_frames, halo_frames, graph=graph,
                            token_id_offset=self.tokens_id_offset)
 
+    def audio_stream(self, sessions: int, push_samples: int, halo_frames: int = None, graph: bool = True,
+                     want_pjt_in: bool = False):
+        """Opt-in, not in the reference: a `streaming.AudioStream` on this codec's engine, for `sessions`
+        utterances whose raw 24 kHz samples arrive a chunk at a time.  `push_tokens(chunks_per_slot,
+        final=..., restart=...)` returns, per slot, the LLM token ids of the frames that became final:
+        the flat frame-major ids `encode` yields (`audio_tokenize`'s absolute ids, `token_id_offset`
+        included), which `token_stream().push_tokens` takes; a slot's ids together are those of its
+        whole clip up to fp32 summation order.  fp32 (the engine's mode)."""
+        from .streaming import AudioStream
+
+        if self.ngroups != 1:
+            raise ValueError("audio_stream emits one group's codes per frame (n_groups == 1)")
+        return AudioStream(self._engine(), sessions, push_samples, halo_frames, graph=graph, want_pjt_in=want_pjt_in,
+                           token_id_offset=self.tokens_id_offset, token_table=self.gr_audio_code2token)
+
     def forward(self, audio_pathes: list):
         """distil_codec.py:518-530 (eval semantics)."""
         audios, mel_specs, gen_time_lengths, n_hop_lengths = self.preprocess_audio_batch(audio_pathes=audio_pathes)

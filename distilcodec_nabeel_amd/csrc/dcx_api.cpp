@@ -53,6 +53,41 @@ bool seg_from_plan(const int32_t* host, const int32_t* dev, int64_t batch, int64
          g.n_t4 <= frames && g.n_run >= batch && g.n_run <= frames;
 }
 
+// The slot form of the descriptor (dcx_tokenize_slots): batch slots of slot_samples samples in the padded
+// layout, the work-item counts those of batch equal clips of that length (dcx_ragged_plan's arithmetic).
+// false: a geometry beyond what the kernels index (dcx_ragged_plan's limits).
+bool seg_from_slots(const dcx_codec* h, int64_t batch, int64_t slot_samples, const int32_t* n_dev, dcx::RaggedSeg& g) {
+  const dcx_config& c = h->cfg;
+  const int64_t pad = (c.win - c.hop) / 2, padr = (c.win - c.hop + 1) / 2;
+  if (batch < 1 || batch > kRaggedMaxBatch || slot_samples < pad || slot_samples > kRaggedMaxSamples / batch) return false;
+  const int64_t wf = frames_of(c, slot_samples + 1);
+  if (wf < 1 || wf > kRaggedMaxFrames / batch) return false;
+  g = dcx::RaggedSeg{};
+  g.batch = (int)batch;
+  g.rows = (int)(batch * wf);
+  g.rw = dcx::dwconv_run_rows(g.rows);
+  g.n_t16 = (int)(batch * ((wf + 15) / 16));
+  g.n_t4 = (int)(batch * ((wf + 3) / 4));
+  g.n_run = (int)(batch * ((wf + g.rw - 1) / g.rw));
+  g.n_dev = n_dev;
+  g.slot_samples = (int)slot_samples;
+  g.slot_frames = (int)wf;
+  g.fr_extra = (int)(pad + padr + 1);
+  g.fr_nfft = c.n_fft;
+  g.fr_hop = c.hop;
+  g.fr_min = (int)pad;
+  return true;
+}
+
+// what both slot entries refuse before their first launch
+int slots_pre(dcx_codec* h, const char* who) {
+  if (h->gemm_mode == DCX_GEMM_F32)
+    return fail(h, DCX_ERR_INVALID_ARG, std::string(who) + " runs in DCX_GEMM_X6 or DCX_GEMM_BF16 (the intermediates are planes)");
+  if (h->split_k >= 2)
+    return fail(h, DCX_ERR_STATE, std::string(who) + " with split-K on: the partial sums share one scratch region");
+  return DCX_OK;
+}
+
 int check_ready(dcx_codec* h, bool need_gen) {
   if (!h) return DCX_ERR_INVALID_ARG;
   if (!h->finalized) return fail(h, DCX_ERR_STATE, "dcx_finalize has not been called");
@@ -375,6 +410,29 @@ int dcx_tokenize_ragged(dcx_codec* h, const float* audio_packed, const int32_t* 
   return tokenize_ragged_rows(h, audio_packed, g, codes, x_pjt_in, quantized_fup, ws, s);
 }
 
+// the call's workspace need, checked before the first launch (a later stage's shortage would otherwise
+// be found after earlier stages have run)
+static int slots_workspace(dcx_codec* h, const dcx::RaggedSeg& g, size_t ws_bytes, const char* who) {
+  Bump dry(nullptr, 0, true);
+  RUN(tokenize_slots_rows(h, nullptr, g, nullptr, nullptr, dry, 0));
+  if (ws_bytes < dry.off)
+    return fail(h, DCX_ERR_WORKSPACE, std::string(who) + ": workspace too small (dcx_ragged_workspace_size(h, batch, batch * slot frames))");
+  return DCX_OK;
+}
+
+int dcx_tokenize_slots(dcx_codec* h, const float* audio, const int32_t* n_samples_dev, int32_t batch,
+                       int64_t slot_samples, int32_t* codes, float* x_pjt_in, void* workspace, size_t ws_bytes,
+                       void* stream) {
+  STAGE_PRE(false);
+  if (!audio || !n_samples_dev || !codes) return fail(h, DCX_ERR_INVALID_ARG, "null buffer");
+  RUN(slots_pre(h, "dcx_tokenize_slots"));
+  dcx::RaggedSeg g{};
+  if (!seg_from_slots(h, batch, slot_samples, n_samples_dev, g))
+    return fail(h, DCX_ERR_INVALID_ARG, "dcx_tokenize_slots: slot_samples below the reflect pad's 384, or more than 2^31 - 1 samples / 2^20 frames in all");
+  RUN(slots_workspace(h, g, ws_bytes, "dcx_tokenize_slots"));
+  return tokenize_slots_rows(h, audio, g, codes, x_pjt_in, ws, s);
+}
+
 // Ragged decode: the padded layout with per-clip lengths in device memory.  The checks
 // both entries share; the kernels' own limits are checked where they are launched (stage_generate).
 static int ragged_decode_pre(dcx_codec* h, const void* in, const int32_t* lengths_dev, int64_t frames_max,
@@ -473,6 +531,103 @@ int dcx_stream_decode_step(dcx_codec* h, void* state, size_t state_bytes, int32_
   if (ws_bytes < dry.off)
     return fail(h, DCX_ERR_INVALID_ARG, "token stream: workspace too small (dcx_workspace_size(h, sessions, push_frames + 2 halo_frames))");
   return stage_stream_step(h, st, new_codes, n_new_dev, flags_dev, wav_out, n_out_dev, n_invalid, ws, s);
+}
+
+// Audio streams: the geometry every entry takes, the views of the caller's state buffer
+// and the slot descriptor of the step's tokenization (its lengths: the plan kernel's len array).
+static dcx::AudioGeom audio_geom(const dcx_codec* h) {
+  const dcx_config& c = h->cfg;
+  return dcx::AudioGeom{c.hop, c.n_fft, (c.win - c.hop) / 2, (c.win - c.hop + 1) / 2};
+}
+
+static bool audio_stream_geometry(const dcx_codec* h, int32_t sessions, int32_t push, int32_t halo, dcx::RaggedSeg* g) {
+  if (!h || sessions < 1 || sessions > dcx::kStreamMaxSessions || push < 1 || push > dcx::kAudioStreamMaxPush || halo < 0 ||
+      halo > dcx::kStreamMaxFrames || h->cfg.hop < 4 || h->cfg.hop % 4 || h->cfg.codebook_dim % 4)
+    return false;
+  dcx::RaggedSeg tmp{};
+  return seg_from_slots(h, sessions, dcx::audio_window_samples(audio_geom(h), halo, push), nullptr, g ? *g : tmp);
+}
+
+static int audio_stream_state(dcx_codec* h, void* state, size_t state_bytes, int32_t sessions, int32_t push, int32_t halo,
+                              int32_t want_pjt_in, dcx::AudioStreamState& st, dcx::RaggedSeg& g) {
+  if (!audio_stream_geometry(h, sessions, push, halo, &g))
+    return fail(h, DCX_ERR_INVALID_ARG, "audio stream: sessions must be in [1, 65535], push_samples in [1, 2^24], halo_frames in [0, 65536], and the windows within 2^31 - 1 samples and 2^20 frames in all");
+  if (!state || (reinterpret_cast<uintptr_t>(state) & 15))
+    return fail(h, DCX_ERR_INVALID_ARG, "audio stream: null or misaligned state buffer (16 bytes)");
+  const size_t need = dcx::audio_stream_state_layout(state, sessions, push, halo, h->n_layers,
+                                                     want_pjt_in ? h->cfg.codebook_dim : 0, audio_geom(h), st);
+  if (state_bytes < need)
+    return fail(h, DCX_ERR_INVALID_ARG, "audio stream: the state buffer holds " + std::to_string(state_bytes) + " bytes, " +
+                                            std::to_string(need) + " needed (dcx_stream_encode_state_size)");
+  g.n_dev = st.len;
+  return DCX_OK;
+}
+
+size_t dcx_stream_encode_state_size(const dcx_codec* h, int32_t sessions, int32_t push_samples, int32_t halo_frames,
+                                    int32_t want_pjt_in) {
+  if (!audio_stream_geometry(h, sessions, push_samples, halo_frames, nullptr)) return 0;
+  dcx::AudioStreamState st{};
+  return dcx::audio_stream_state_layout(nullptr, sessions, push_samples, halo_frames, h->n_layers,
+                                        want_pjt_in ? h->cfg.codebook_dim : 0, audio_geom(h), st);
+}
+
+int dcx_stream_encode_geometry(const dcx_codec* h, int32_t push_samples, int32_t halo_frames, int64_t* window_samples,
+                               int64_t* window_frames, int64_t* out_frames) {
+  if (!h || push_samples < 1 || push_samples > dcx::kAudioStreamMaxPush || halo_frames < 0 || halo_frames > dcx::kStreamMaxFrames)
+    return DCX_ERR_INVALID_ARG;
+  const dcx::AudioGeom g = audio_geom(h);
+  const int64_t ws = dcx::audio_window_samples(g, halo_frames, push_samples);
+  if (window_samples) *window_samples = ws;
+  if (window_frames) *window_frames = ws / g.hop;
+  if (out_frames) *out_frames = dcx::audio_take_max(g, halo_frames, push_samples);
+  return DCX_OK;
+}
+
+int dcx_stream_encode_plan_step(const dcx_codec* h, int32_t halo_frames, int32_t push_samples, int32_t* M, int32_t* C,
+                                int32_t* closed, int32_t n_new, int32_t flags, int32_t* len, int32_t* start,
+                                int32_t* skip, int32_t* take) {
+  if (!h || halo_frames < 0 || push_samples < 1 || !M || !C || !closed) return DCX_ERR_INVALID_ARG;
+  dcx::AudioSlot s{*M, *C, *closed};
+  const dcx::AudioStep o = dcx::audio_plan_step(audio_geom(h), halo_frames, push_samples, s, n_new, flags);
+  *M = s.M;
+  *C = s.C;
+  *closed = s.closed;
+  if (len) *len = o.len;
+  if (start) *start = o.start;
+  if (skip) *skip = o.skip;
+  if (take) *take = o.take;
+  return DCX_OK;
+}
+
+int dcx_stream_encode_reset(dcx_codec* h, void* state, size_t state_bytes, int32_t sessions, int32_t push_samples,
+                            int32_t halo_frames, int32_t want_pjt_in, void* stream) {
+  if (!h) return DCX_ERR_INVALID_ARG;
+  dcx::AudioStreamState st{};
+  dcx::RaggedSeg g{};
+  RUN(audio_stream_state(h, state, state_bytes, sessions, push_samples, halo_frames, want_pjt_in, st, g));
+  RUN(check_ready(h, false));
+  HIPCHK(h, dcx::launch_audio_stream_reset(st, (hipStream_t)stream));
+  return DCX_OK;
+}
+
+int dcx_stream_encode_step(dcx_codec* h, void* state, size_t state_bytes, int32_t sessions, int32_t push_samples,
+                           int32_t halo_frames, const float* new_samples, const int32_t* n_new_dev,
+                           const int32_t* flags_dev, int32_t* codes_out, int32_t* n_out_dev, float* x_pjt_in_out,
+                           void* workspace, size_t ws_bytes, void* stream) {
+  if (!h) return DCX_ERR_INVALID_ARG;
+  dcx::AudioStreamState st{};
+  dcx::RaggedSeg g{};
+  // a state buffer laid out with the x_pjt_in window exactly when the caller takes x_pjt_in
+  RUN(audio_stream_state(h, state, state_bytes, sessions, push_samples, halo_frames, x_pjt_in_out ? 1 : 0, st, g));
+  if (!new_samples || !n_new_dev || !flags_dev || !codes_out || !n_out_dev ||
+      (reinterpret_cast<uintptr_t>(x_pjt_in_out) & 15))
+    return fail(h, DCX_ERR_INVALID_ARG, "audio stream: null buffer, or x_pjt_in_out not on a 16-byte boundary");
+  const int32_t batch = sessions;
+  STAGE_PRE(false);
+  // what the tokenization would refuse after the plan kernel has run is refused here, before any launch
+  RUN(slots_pre(h, "dcx_stream_encode_step"));
+  RUN(slots_workspace(h, g, ws_bytes, "dcx_stream_encode_step"));
+  return stage_audio_stream_step(h, st, g, new_samples, n_new_dev, flags_dev, codes_out, n_out_dev, x_pjt_in_out, ws, s);
 }
 
 int dcx_module_io(const dcx_codec* h, const char* module, int32_t* in_channels, int32_t* out_channels,

@@ -456,6 +456,11 @@ int stage_encode_decode(dcx_codec* h, const float* audio, int B, int64_t n, int3
 int stage_decode_ragged(dcx_codec* h, const int32_t* codes, const int* lens, int B, int T, float* wav,
                         int32_t* n_invalid, Bump& ws, hipStream_t s);
 // one step of a token stream on the state st views: n_invalid counts the codes the step appends
+int tokenize_slots_rows(dcx_codec* h, const float* audio, const dcx::RaggedSeg& rg, int32_t* codes, float* pin, Bump& ws,
+                        hipStream_t s);
+int stage_audio_stream_step(dcx_codec* h, const dcx::AudioStreamState& st, const dcx::RaggedSeg& rg,
+                            const float* new_samples, const int* n_new, const int* flags, int32_t* codes_out, int* n_out,
+                            float* pin_out, Bump& ws, hipStream_t s);
 int stage_stream_step(dcx_codec* h, const dcx::StreamState& st, const int32_t* new_codes, const int* n_new,
                       const int* flags, float* wav_out, int* n_out, int32_t* n_invalid, Bump& ws, hipStream_t s);
 

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dcx_stream_plan.h"
+
 namespace dcx {
 
 // Epilogue of the implicit-GEMM convolution (applied per output element v = acc + bias).
@@ -418,11 +420,22 @@ bool bf16dm_takes(int cin, int cout, int lq, int ldx, int phases);
 // cu_run its runs of rw rows (rw chosen from the total row count as launch_dwconv_ln chooses it).
 // The five prefix arrays ([batch + 1] ints each) are device pointers into the uploaded plan table; the
 // totals are the host's copy of their last entries.
+// The slot form (n_dev non-null; dcx_tokenize_slots): the padded layout instead, `batch` equal slots of
+// slot_samples samples and slot_frames rows, slot b holding n_dev[b] samples (DEVICE memory, clamped by
+// the kernels to [0, slot_samples]) and the rows a clip of that many samples has alone: none below
+// fr_min samples, else (n + fr_extra - fr_nfft) / fr_hop + 1 (dcx_num_frames(n + 1)).  The prefix arrays
+// are then null, the work items are enumerated over every slot's whole row count (rows, n_t16, n_t4,
+// n_run: batch times a slot's), and the rows beyond a slot's length are written as zeros.
 struct RaggedSeg {
   const int *cu_samples, *cu_frames, *cu_t16, *cu_t4, *cu_run;
   int batch, rw;
   int rows, n_t16, n_t4, n_run;
+  const int* n_dev;
+  int slot_samples, slot_frames, fr_extra, fr_nfft, fr_hop, fr_min;
 };
+// rows [r0, r0 + frames) of slot b of codes [batch][frames][R] set to -1 and of pin [batch][frames][dim]
+// (may be null) to zero, r0 the slot's length as the slot form of RaggedSeg defines it
+hipError_t launch_slots_mask(const RaggedSeg& g, int32_t* codes, int R, float* pin, int dim, hipStream_t s);
 // rows per register-ring run of a dwconv_ln launch of `rows` rows (launch_dwconv_ln's rule)
 inline int dwconv_run_rows(long long rows) {
   return rows >= 2048LL * 32 ? 32 : rows >= 2048LL * 16 ? 16 : rows >= 2048LL * 8 ? 8 : 4;
@@ -548,6 +561,59 @@ hipError_t launch_stream_window(const StreamState& st, const int32_t* new_codes,
 // out[b] = the window waveform's frames [skip, skip + take), then zeros up to (push + halo) * hop samples;
 // n_out[b] = take; the slot's counters take the values the plan kernel left
 hipError_t launch_stream_emit(const StreamState& st, float* out, int* n_out, hipStream_t s);
+// ---- audio streams (dcx_stream.hip; DESIGN.md §3 "Audio streams") ----
+// The caller's state buffer of `sessions` slots, push size P (raw samples), halo h (frames): twelve
+// [sessions] int arrays (the counters of dcx_stream_plan.h's AudioSlot, the counters a step leaves, the
+// step's outputs), the sample ring [sessions][Ws] (raw sample r at r % Ws), the step's window
+// [sessions][Ws], its codes [sessions][Wf][R] and, when asked for (CD > 0), its x_pjt_in
+// [sessions][Wf][CD], each part on a 256-byte boundary.  Ws = audio_window_samples, Wf = Ws / hop its
+// frames, K = audio_take_max the rows of the step's outputs.
+struct AudioStreamState {
+  int *M, *C, *closed;
+  int *M_next, *C_next, *closed_next;
+  int *len, *start, *skip, *take, *m_old, *n;  // the step's outputs
+  float *ring, *window;
+  int32_t* codes;
+  float* pin;
+  int sessions, push, halo, Ws, Wf, K, R, CD;
+  AudioGeom geo;
+};
+constexpr int kAudioStreamCounters = 12;
+constexpr int kAudioStreamMaxPush = 1 << 24;  // samples
+inline size_t audio_stream_state_layout(void* base, int sessions, int push, int halo, int R, int CD, const AudioGeom& geo,
+                                        AudioStreamState& st) {
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t B = (size_t)sessions, Ws = (size_t)audio_window_samples(geo, halo, push), Wf = Ws / geo.hop;
+  char* p = (char*)base;
+  size_t off = 0;
+  int** ctr[kAudioStreamCounters] = {&st.M, &st.C, &st.closed, &st.M_next, &st.C_next, &st.closed_next,
+                                     &st.len, &st.start, &st.skip, &st.take, &st.m_old, &st.n};
+  for (int i = 0; i < kAudioStreamCounters; ++i) *ctr[i] = (int*)(p + off + i * B * sizeof(int));
+  off = up(off + kAudioStreamCounters * B * sizeof(int));
+  st.ring = (float*)(p + off);
+  off = up(off + B * Ws * sizeof(float));
+  st.window = (float*)(p + off);
+  off = up(off + B * Ws * sizeof(float));
+  st.codes = (int32_t*)(p + off);
+  off = up(off + B * Wf * R * sizeof(int32_t));
+  st.pin = CD > 0 ? (float*)(p + off) : nullptr;
+  if (CD > 0) off = up(off + B * Wf * CD * sizeof(float));
+  st.sessions = sessions; st.push = push; st.halo = halo; st.Ws = (int)Ws; st.Wf = (int)Wf;
+  st.K = (int)audio_take_max(geo, halo, push); st.R = R; st.CD = CD; st.geo = geo;
+  return off;
+}
+// every slot empty (the counters zeroed; the ring is only read where a step wrote it)
+hipError_t launch_audio_stream_reset(const AudioStreamState& st, hipStream_t s);
+// one thread per slot: audio_plan_step on the slot's counters with n_new[b] / flags[b] (device)
+hipError_t launch_audio_stream_plan(const AudioStreamState& st, const int* n_new, const int* flags, hipStream_t s);
+// the step's n samples of new_samples [sessions][push] appended to the ring, and window[b][j] = raw sample
+// start + j for j < len (zeros beyond), from the ring or from the samples this step appends
+hipError_t launch_audio_stream_window(const AudioStreamState& st, const float* new_samples, hipStream_t s);
+// codes_out[b] = the window's code rows [skip, skip + take), then -1 up to K rows; pin_out (may be null)
+// the same rows of the window's x_pjt_in, then zeros; n_out[b] = take; the slot's counters take the
+// values the plan kernel left
+hipError_t launch_audio_stream_emit(const AudioStreamState& st, int32_t* codes_out, int* n_out, float* pin_out,
+                                    hipStream_t s);
 
 hipError_t launch_transpose(const float* in, float* out, int batch, long long rows, long long cols, hipStream_t s);
 hipError_t launch_resample_poly(const float* x, int batch, long long n_in, long long xs, const double* h, int hlen,

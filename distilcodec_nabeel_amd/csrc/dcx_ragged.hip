@@ -10,6 +10,10 @@
 //    enumerated per clip from the plan's prefix sums.
 // All are streaming kernels with 16-byte accesses along the contiguous axis; a work item finds its
 // clip by a binary search of a [batch + 1] prefix array (L2-resident, log2(batch) reads).
+// The slot form (SL, dcx_tokenize_slots; RaggedSeg::n_dev): the padded layout, batch equal slots whose
+// sample counts are read from device memory.  A work item finds its slot by a division, takes the
+// slot's length L from n_dev and writes the rows from L to the slot's end as zeros; everything else is
+// the packed form's code, so a slot's live rows get the arithmetic a clip of that length gets alone.
 #include "dcx_kernels.h"
 #include "dcx_planes.h"
 #include "dcx_ln.h"
@@ -29,11 +33,41 @@ __device__ __forceinline__ int seg_find(const int* __restrict__ cu, int batch, i
   return lo;
 }
 
+// slot form: the slot's sample count (clamped) and the frames a clip of n samples has alone
+// (dcx_num_frames(n + 1); none below the reflect pad's length, dcx_ragged_plan's rule)
+__device__ __forceinline__ int slot_samples(const RaggedSeg& g, int b) { return min(max(g.n_dev[b], 0), g.slot_samples); }
+__device__ __forceinline__ int slot_rows(const RaggedSeg& g, int n) {
+  const int len = n + g.fr_extra;
+  return n < g.fr_min || len < g.fr_nfft ? 0 : (len - g.fr_nfft) / g.fr_hop + 1;
+}
+
+// a dwconv_ln output row beyond its slot's length: zeros in every form (an h2 row with the shift and
+// the maximum of a zero row), one wave per row as ln_finish
+template <int NV>
+__device__ __forceinline__ void ln_zero_row(int C, float* __restrict__ y, unsigned short* __restrict__ y6, Layout lay,
+                                            long long row, int lane, int* __restrict__ ash_row,
+                                            float* __restrict__ amax_row) {
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int c = (lane + 64 * i) * 4;
+    if (y) *reinterpret_cast<f32x4*>(y + row * C + c) = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (!y6) continue;
+    if (lay == LAYOUT_BF16) store_bf16x4(y6, row, C, c, 0.f, 0.f, 0.f, 0.f);
+    else if (lay == LAYOUT_H2) store_h2_4(y6, row, C, c, 0.f, 0.f, 0.f, 0.f);
+    else store_planes4(y6, row, C, c, 0.f, 0.f, 0.f, 0.f);
+  }
+  if (y6 && lay == LAYOUT_H2 && lane == 0) {
+    ash_row[row] = h2_shift(0.f);
+    if (amax_row) amax_row[row] = 0.f;
+  }
+}
+
 // ---------------------------------------------------------------------------------------------
 // STFT framing.  Clip b's padded signal is [0, x_0 .. x_{n-1}] (the reference's one-sample left pad,
 // distil_codec.py:133-136), reflect-padded by `pad` on both sides (mel_spec.py:30-37); frame t holds
 // its samples t * hop - pad .. + n_fft - 1.  One thread writes 4 samples of one frame.
 // ---------------------------------------------------------------------------------------------
+template <bool SL>
 __global__ void __launch_bounds__(256) ragged_frames_kernel(const float* __restrict__ audio, const RaggedSeg g,
                                                              float* __restrict__ frames,
                                                              unsigned short* __restrict__ frames6, int n_fft, int hop,
@@ -43,17 +77,29 @@ __global__ void __launch_bounds__(256) ragged_frames_kernel(const float* __restr
   for (long long i4 = (long long)blockIdx.x * blockDim.x + threadIdx.x; i4 < total4;
        i4 += (long long)gridDim.x * blockDim.x) {
     const int row = (int)(i4 / per), j = (int)(i4 - (long long)row * per) * 4;
-    const int b = seg_find(g.cu_frames, g.batch, row);
-    const int t = row - g.cu_frames[b];
-    const long long s0 = g.cu_samples[b];
-    const long long n = (long long)g.cu_samples[b + 1] - s0 + 1;  // with the leading zero
+    int b, t;
+    long long s0, n;  // n: with the leading zero
+    bool live = true;
+    if constexpr (SL) {
+      b = row / g.slot_frames;
+      t = row - b * g.slot_frames;
+      s0 = (long long)b * g.slot_samples;
+      const int nb = slot_samples(g, b);
+      n = (long long)nb + 1;
+      live = t < slot_rows(g, nb);  // a row beyond the slot's length: zeros, nothing read
+    } else {
+      b = seg_find(g.cu_frames, g.batch, row);
+      t = row - g.cu_frames[b];
+      s0 = g.cu_samples[b];
+      n = (long long)g.cu_samples[b + 1] - s0 + 1;
+    }
     float v[4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       long long src = (long long)t * hop + j + e - pad;
       if (src < 0) src = -src;
       if (src >= n) src = 2 * (n - 1) - src;
-      v[e] = src > 0 ? audio[s0 + src - 1] : 0.f;
+      v[e] = live && src > 0 ? audio[s0 + src - 1] : 0.f;
     }
     if (frames) *reinterpret_cast<f32x4*>(frames + (long long)row * n_fft + j) = f32x4{v[0], v[1], v[2], v[3]};
     if (frames6) store_planes4(frames6, row, n_fft, j, v[0], v[1], v[2], v[3]);
@@ -65,7 +111,10 @@ hipError_t launch_ragged_frames(const float* audio, const RaggedSeg& g, float* f
   if (n_fft % 8 || g.rows < 1 || g.batch < 1) return hipErrorInvalidValue;
   const long long total4 = (long long)g.rows * (n_fft / 4);
   const unsigned gx = (unsigned)std::min<long long>((total4 + 255) / 256, 65536);
-  hipLaunchKernelGGL(ragged_frames_kernel, dim3(gx), dim3(256), 0, s, audio, g, frames, frames6, n_fft, hop, pad);
+  if (g.n_dev)
+    hipLaunchKernelGGL(ragged_frames_kernel<true>, dim3(gx), dim3(256), 0, s, audio, g, frames, frames6, n_fft, hop, pad);
+  else
+    hipLaunchKernelGGL(ragged_frames_kernel<false>, dim3(gx), dim3(256), 0, s, audio, g, frames, frames6, n_fft, hop, pad);
   return hipGetLastError();
 }
 
@@ -76,19 +125,29 @@ hipError_t launch_ragged_frames(const float* audio, const RaggedSeg& g, float* f
 // ---------------------------------------------------------------------------------------------
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
+template <bool SL>
 __global__ void __launch_bounds__(256) ragged_unfold_kernel(const u32x4* __restrict__ x, u32x4* __restrict__ y,
                                                              const RaggedSeg g, int units, int taps) {
   const int lane = threadIdx.x & 63;
   const int nwaves = gridDim.x * 4;
   for (int row = blockIdx.x * 4 + (threadIdx.x >> 6); row < g.rows; row += nwaves) {  // wave-uniform
-    const int b = seg_find(g.cu_frames, g.batch, row);
-    const int r0 = g.cu_frames[b], r1 = g.cu_frames[b + 1];
+    int r0, r1;
+    bool live = true;
+    if constexpr (SL) {
+      const int b = row / g.slot_frames;
+      r0 = b * g.slot_frames;
+      r1 = r0 + slot_rows(g, slot_samples(g, b));
+      live = row < r1;  // a row beyond the slot's length: zeros
+    } else {
+      const int b = seg_find(g.cu_frames, g.batch, row);
+      r0 = g.cu_frames[b], r1 = g.cu_frames[b + 1];
+    }
     u32x4* dst = y + (long long)row * taps * units;
     for (int i = lane; i < taps * units; i += 64) {
       const int j = i / units, u = i - j * units;
       const int src = row + j - taps / 2;
       u32x4 v = {0u, 0u, 0u, 0u};
-      if (src >= r0 && src < r1) v = x[(long long)src * units + u];
+      if (live && src >= r0 && src < r1) v = x[(long long)src * units + u];
       dst[i] = v;
     }
   }
@@ -98,8 +157,12 @@ hipError_t launch_ragged_unfold(const void* x, void* y, const RaggedSeg& g, int 
   if (row_bytes < 16 || row_bytes % 16 || taps < 1 || taps % 2 == 0 || g.rows < 1 || g.batch < 1)
     return hipErrorInvalidValue;
   const unsigned gx = (unsigned)std::min((g.rows + 3) / 4, 16384);
-  hipLaunchKernelGGL(ragged_unfold_kernel, dim3(gx), dim3(256), 0, s, reinterpret_cast<const u32x4*>(x),
-                     reinterpret_cast<u32x4*>(y), g, row_bytes / 16, taps);
+  if (g.n_dev)
+    hipLaunchKernelGGL(ragged_unfold_kernel<true>, dim3(gx), dim3(256), 0, s, reinterpret_cast<const u32x4*>(x),
+                       reinterpret_cast<u32x4*>(y), g, row_bytes / 16, taps);
+  else
+    hipLaunchKernelGGL(ragged_unfold_kernel<false>, dim3(gx), dim3(256), 0, s, reinterpret_cast<const u32x4*>(x),
+                       reinterpret_cast<u32x4*>(y), g, row_bytes / 16, taps);
   return hipGetLastError();
 }
 
@@ -109,7 +172,7 @@ hipError_t launch_ragged_unfold(const void* x, void* y, const RaggedSeg& g, int 
 // tile's own clip's frame count, so the halo rows beyond the clip are staged as zeros and their taps
 // dropped exactly as for a clip alone.
 // ---------------------------------------------------------------------------------------------
-template <int NV, int DW_R>
+template <int NV, int DW_R, bool SL>
 __global__ void __launch_bounds__(256) dwconv_ln_seg_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                              unsigned short* __restrict__ y6, Layout lay,
                                                              const float* __restrict__ dww, const float* __restrict__ dwb,
@@ -119,10 +182,25 @@ __global__ void __launch_bounds__(256) dwconv_ln_seg_kernel(const float* __restr
   constexpr int C = 256 * NV, C4 = C / 4, ROWS = DW_R + 6;
   __shared__ f32x4 tile[ROWS * C4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int bidx = seg_find(cu_tiles, g.batch, (int)blockIdx.x);
-  const int t0 = ((int)blockIdx.x - cu_tiles[bidx]) * DW_R;
-  const long long base = g.cu_frames[bidx];
-  const int L = g.cu_frames[bidx + 1] - (int)base;
+  int t0, L;
+  long long base;
+  if constexpr (SL) {  // the slot's tiles over its whole row count; L: the rows that hold data
+    const int per = (g.slot_frames + DW_R - 1) / DW_R;
+    const int bidx = (int)blockIdx.x / per;
+    t0 = ((int)blockIdx.x - bidx * per) * DW_R;
+    base = (long long)bidx * g.slot_frames;
+    L = slot_rows(g, slot_samples(g, bidx));
+    for (int rr = wave; rr < DW_R; rr += 4) {
+      const int t = t0 + rr;
+      if (t >= L && t < g.slot_frames) ln_zero_row<NV>(C, y, y6, lay, base + t, lane, ash_row, amax_row);
+    }
+    if (t0 >= L) return;  // wholly beyond the slot's length: before any load (and the block's barrier)
+  } else {
+    const int bidx = seg_find(cu_tiles, g.batch, (int)blockIdx.x);
+    t0 = ((int)blockIdx.x - cu_tiles[bidx]) * DW_R;
+    base = g.cu_frames[bidx];
+    L = g.cu_frames[bidx + 1] - (int)base;
+  }
   const float* xb = x + base * C;
   // stage rows t0 - 3 .. t0 + DW_R + 2 (all loads issued before any LDS store)
   constexpr int PER = (ROWS * C4 + 255) / 256;
@@ -180,7 +258,7 @@ __global__ void __launch_bounds__(256) dwconv_ln_seg_kernel(const float* __restr
 // Register-ring form (launches of >= 8192 rows): dwconv_ln_run_kernel with the wave's run looked up
 // in cu_run; a run is RW consecutive rows of one clip (the last run of a clip may be shorter).
 // ---------------------------------------------------------------------------------------------
-template <int NV, int RW, int D>
+template <int NV, int RW, int D, bool SL>
 __global__ void __launch_bounds__(256) dwconv_ln_run_seg_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                                  unsigned short* __restrict__ y6, Layout lay,
                                                                  const float* __restrict__ dww,
@@ -198,10 +276,24 @@ __global__ void __launch_bounds__(256) dwconv_ln_run_seg_kernel(const float* __r
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int run = (int)blockIdx.x * 4 + wave;
   if (run >= g.n_run) return;  // whole wave, after the block's only barrier
-  const int bidx = seg_find(g.cu_run, g.batch, run);
-  const long long base = g.cu_frames[bidx];
-  const int L = g.cu_frames[bidx + 1] - (int)base;
-  const int t0 = (run - g.cu_run[bidx]) * RW, t1 = min(t0 + RW, L);
+  int t0, L;
+  long long base;
+  if constexpr (SL) {  // the slot's runs over its whole row count; L: the rows that hold data
+    const int per = (g.slot_frames + RW - 1) / RW;
+    const int bidx = run / per;
+    t0 = (run - bidx * per) * RW;
+    base = (long long)bidx * g.slot_frames;
+    L = slot_rows(g, slot_samples(g, bidx));
+    for (int t = max(t0, L); t < min(t0 + RW, g.slot_frames); ++t)
+      ln_zero_row<NV>(C, y, y6, lay, base + t, lane, ash_row, amax_row);
+    if (t0 >= L) return;  // wholly beyond the slot's length: before any load
+  } else {
+    const int bidx = seg_find(g.cu_run, g.batch, run);
+    base = g.cu_frames[bidx];
+    L = g.cu_frames[bidx + 1] - (int)base;
+    t0 = (run - g.cu_run[bidx]) * RW;
+  }
+  const int t1 = min(t0 + RW, L);
   const float* xb = x + base * C;
   f32x4 win[S][NV], bv[NV];
 #pragma unroll
@@ -260,12 +352,18 @@ static void launch_run_seg_nv(const float* x, float* y, unsigned short* y6, Layo
                               int* ash_row, float* amax_row) {
   const dim3 grid((unsigned)((g.n_run + 3) / 4)), block(256);
   constexpr int D = NV >= 4 ? 1 : 2;  // as launch_dwconv_ln_nv
+#define DCX_RUN_SEG(RW)                                                                                                   \
+  if (g.n_dev)                                                                                                           \
+    hipLaunchKernelGGL((dwconv_ln_run_seg_kernel<NV, RW, D, true>), grid, block, 0, s, DCX_RAGGED_ARGS, bf, ash_row, amax_row); \
+  else                                                                                                                   \
+    hipLaunchKernelGGL((dwconv_ln_run_seg_kernel<NV, RW, D, false>), grid, block, 0, s, DCX_RAGGED_ARGS, bf, ash_row, amax_row)
   switch (g.rw) {
-    case 32: hipLaunchKernelGGL((dwconv_ln_run_seg_kernel<NV, 32, D>), grid, block, 0, s, DCX_RAGGED_ARGS, bf, ash_row, amax_row); break;
-    case 16: hipLaunchKernelGGL((dwconv_ln_run_seg_kernel<NV, 16, D>), grid, block, 0, s, DCX_RAGGED_ARGS, bf, ash_row, amax_row); break;
-    case 8: hipLaunchKernelGGL((dwconv_ln_run_seg_kernel<NV, 8, D>), grid, block, 0, s, DCX_RAGGED_ARGS, bf, ash_row, amax_row); break;
-    default: hipLaunchKernelGGL((dwconv_ln_run_seg_kernel<NV, 4, D>), grid, block, 0, s, DCX_RAGGED_ARGS, bf, ash_row, amax_row); break;
+    case 32: DCX_RUN_SEG(32); break;
+    case 16: DCX_RUN_SEG(16); break;
+    case 8: DCX_RUN_SEG(8); break;
+    default: DCX_RUN_SEG(4); break;
   }
+#undef DCX_RUN_SEG
 }
 
 template <int NV>
@@ -273,10 +371,16 @@ static void launch_tiled_seg_nv(const float* x, float* y, unsigned short* y6, La
                                 const float* dwb, const float* lnw, const float* lnb, const RaggedSeg& g, bool small,
                                 int bf, hipStream_t s, int* ash_row, float* amax_row) {
   const dim3 block(256);
-  if (small)
-    hipLaunchKernelGGL((dwconv_ln_seg_kernel<NV, 4>), dim3((unsigned)g.n_t4), block, 0, s, DCX_RAGGED_ARGS, g.cu_t4, bf, ash_row, amax_row);
-  else
-    hipLaunchKernelGGL((dwconv_ln_seg_kernel<NV, 16>), dim3((unsigned)g.n_t16), block, 0, s, DCX_RAGGED_ARGS, g.cu_t16, bf, ash_row, amax_row);
+  if (g.n_dev) {
+    if (small)
+      hipLaunchKernelGGL((dwconv_ln_seg_kernel<NV, 4, true>), dim3((unsigned)g.n_t4), block, 0, s, DCX_RAGGED_ARGS, nullptr, bf, ash_row, amax_row);
+    else
+      hipLaunchKernelGGL((dwconv_ln_seg_kernel<NV, 16, true>), dim3((unsigned)g.n_t16), block, 0, s, DCX_RAGGED_ARGS, nullptr, bf, ash_row, amax_row);
+  } else if (small) {
+    hipLaunchKernelGGL((dwconv_ln_seg_kernel<NV, 4, false>), dim3((unsigned)g.n_t4), block, 0, s, DCX_RAGGED_ARGS, g.cu_t4, bf, ash_row, amax_row);
+  } else {
+    hipLaunchKernelGGL((dwconv_ln_seg_kernel<NV, 16, false>), dim3((unsigned)g.n_t16), block, 0, s, DCX_RAGGED_ARGS, g.cu_t16, bf, ash_row, amax_row);
+  }
 }
 
 hipError_t launch_dwconv_ln_ragged(const float* x, float* y, unsigned short* y6, Layout lay, const float* dww,
@@ -310,5 +414,30 @@ hipError_t launch_dwconv_ln_ragged(const float* x, float* y, unsigned short* y6,
 }
 
 #undef DCX_RAGGED_ARGS
+
+// ---------------------------------------------------------------------------------------------
+// The slot form's results beyond each slot's length: codes -1, x_pjt_in rows zero (the row-wise steps
+// ran on those rows too).  One wave per row; a live row is left as it is.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) slots_mask_kernel(const RaggedSeg g, int32_t* __restrict__ codes, int R,
+                                                          float* __restrict__ pin, int dim) {
+  const int lane = threadIdx.x & 63;
+  const int nwaves = gridDim.x * 4;
+  for (int row = blockIdx.x * 4 + (threadIdx.x >> 6); row < g.rows; row += nwaves) {  // wave-uniform
+    const int b = row / g.slot_frames;
+    if (row - b * g.slot_frames < slot_rows(g, slot_samples(g, b))) continue;
+    for (int r = lane; r < R; r += 64) codes[(long long)row * R + r] = -1;
+    if (pin)
+      for (int c = lane * 4; c < dim; c += 256)
+        *reinterpret_cast<f32x4*>(pin + (long long)row * dim + c) = f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+}
+
+hipError_t launch_slots_mask(const RaggedSeg& g, int32_t* codes, int R, float* pin, int dim, hipStream_t s) {
+  if (!g.n_dev || !codes || g.rows < 1 || g.slot_frames < 1 || R < 1 || dim < 4 || dim % 4) return hipErrorInvalidValue;
+  const unsigned gx = (unsigned)std::min((g.rows + 3) / 4, 16384);
+  hipLaunchKernelGGL(slots_mask_kernel, dim3(gx), dim3(256), 0, s, g, codes, R, pin, dim);
+  return hipGetLastError();
+}
 
 }  // namespace dcx

@@ -549,6 +549,33 @@ int stage_stream_step(dcx_codec* h, const dcx::StreamState& st, const int32_t* n
   return DCX_OK;
 }
 
+// dcx_tokenize_slots: tokenize_ragged_rows on the slot form of rg (every row of the padded layout, the
+// three clip-aware steps bounded by the slots' device-side lengths), then the results beyond each
+// slot's length set to -1 / zero.
+int tokenize_slots_rows(dcx_codec* h, const float* audio, const dcx::RaggedSeg& rg, int32_t* codes, float* pin, Bump& ws,
+                        hipStream_t s) {
+  RUN(tokenize_ragged_rows(h, audio, rg, codes, pin, nullptr, ws, s));
+  if (ws.dry) return DCX_OK;
+  LAUNCH(h, s, "slots_mask", 0, 0, dcx::launch_slots_mask(rg, codes, h->n_layers, pin, h->cfg.codebook_dim, s));
+  return DCX_OK;
+}
+
+// One step of an audio stream (dcx_stream_encode_step): the slots' plan, their windows of samples, the
+// slot tokenization of the windows with the plan's lengths, and the emitted codes.  The emit kernel
+// commits the slots' counters, so a step that fails before it leaves the state as it was.
+int stage_audio_stream_step(dcx_codec* h, const dcx::AudioStreamState& st, const dcx::RaggedSeg& rg,
+                            const float* new_samples, const int* n_new, const int* flags, int32_t* codes_out, int* n_out,
+                            float* pin_out, Bump& ws, hipStream_t s) {
+  const double samples = (double)st.sessions * st.Ws;
+  LAUNCH(h, s, "audio_stream_plan", 0, 4.0 * dcx::kAudioStreamCounters * st.sessions,
+         dcx::launch_audio_stream_plan(st, n_new, flags, s));
+  LAUNCH(h, s, "audio_stream_window", 0, 8.0 * samples, dcx::launch_audio_stream_window(st, new_samples, s));
+  RUN(tokenize_slots_rows(h, st.window, rg, st.codes, st.pin, ws, s));
+  LAUNCH(h, s, "audio_stream_emit", 0, 8.0 * st.sessions * st.K * (st.R + (pin_out ? st.CD : 0)),
+         dcx::launch_audio_stream_emit(st, codes_out, n_out, pin_out, s));
+  return DCX_OK;
+}
+
 // Half-batches on two streams (Knobs::enc_streams >= 2; 1 forks inside the encoder only): clips
 // [0, B0) on the caller's stream and [B0, B) on the side stream, each in its own part of the
 // workspace (half 0's, then half 1's: the sizes are linear in the clip count).  Every stage computes

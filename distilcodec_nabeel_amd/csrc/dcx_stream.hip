@@ -115,4 +115,138 @@ hipError_t launch_stream_emit(const StreamState& st, float* out, int* n_out, hip
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// Audio streams (dcx_stream_encode_step; DESIGN.md §3 "Audio streams"): the same three kernels around
+// the slot tokenization of one step.
+//  * audio_stream_plan: audio_plan_step per slot;
+//  * audio_stream_window: the step's samples appended to the sample ring (raw sample r at r % Ws) and the
+//    slot's window, raw samples [start, M), from the ring and the appended samples.  A window is at
+//    most Ws consecutive samples, so the ring positions read (samples below the old M) and written
+//    (from it on) are distinct.  start and Ws are multiples of 4, so a window unit of 4 samples that
+//    lies in the ring is one 16-byte copy; the appended samples start anywhere in the ring, so they
+//    are 16-byte where both sides are aligned;
+//  * audio_stream_emit: the emitted rows of the window's codes (and x_pjt_in), -1 (zeros) behind
+//    them, and the commit of the counters.
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) audio_stream_plan_kernel(const AudioStreamState st, const int* __restrict__ n_new,
+                                                                 const int* __restrict__ flags) {
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= st.sessions) return;
+  AudioSlot s{st.M[b], st.C[b], st.closed[b]};
+  const AudioStep o = audio_plan_step(st.geo, st.halo, st.push, s, n_new[b], flags[b]);
+  st.M_next[b] = s.M;
+  st.C_next[b] = s.C;
+  st.closed_next[b] = s.closed;
+  st.len[b] = o.len;
+  st.start[b] = o.start;
+  st.skip[b] = o.skip;
+  st.take[b] = o.take;
+  st.m_old[b] = o.m_old;
+  st.n[b] = o.n;
+}
+
+// one thread per 4 samples: unit u of the slot's ring (the append) and of its window (the copy)
+__global__ void __launch_bounds__(256) audio_stream_window_kernel(const AudioStreamState st,
+                                                                   const float* __restrict__ new_samples) {
+  const int b = blockIdx.y;
+  const int j0 = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
+  const int Ws = st.Ws;
+  if (j0 >= Ws) return;
+  const int m_old = st.m_old[b], n = min(max(st.n[b], 0), st.push);
+  const int start = st.start[b], len = min(max(st.len[b], 0), min(Ws, m_old + n - start));
+  float* ring = st.ring + (size_t)b * Ws;
+  const float* nw = new_samples + (size_t)b * st.push;
+  {  // ring positions j0 .. j0 + 3 hold appended samples i0 .. (mod Ws) where those lie below n
+    const int r0 = m_old % Ws;
+    const int i0 = j0 >= r0 ? j0 - r0 : j0 - r0 + Ws;
+    if (i0 <= n - 4) {  // no wrap inside the unit: i0 + 3 < n <= Ws
+      f32x4s v;
+      if ((reinterpret_cast<uintptr_t>(nw + i0) & 15) == 0) v = *reinterpret_cast<const f32x4s*>(nw + i0);
+      else v = f32x4s{nw[i0], nw[i0 + 1], nw[i0 + 2], nw[i0 + 3]};
+      *reinterpret_cast<f32x4s*>(ring + j0) = v;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const int i = i0 + e >= Ws ? i0 + e - Ws : i0 + e;
+        if (i < n) ring[j0 + e] = nw[i];
+      }
+    }
+  }
+  f32x4s w = {0.f, 0.f, 0.f, 0.f};
+  if (j0 + 3 < len && start + j0 + 3 < m_old) {
+    w = *reinterpret_cast<const f32x4s*>(ring + (start + j0) % Ws);
+  } else {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int p = start + j0 + e;  // < M = m_old + n where j0 + e < len
+      if (j0 + e < len) w[e] = p < m_old ? ring[p % Ws] : nw[p - m_old];
+    }
+  }
+  *reinterpret_cast<f32x4s*>(st.window + (size_t)b * Ws + j0) = w;
+}
+
+// one thread per code of the output, and per 4 values of its x_pjt_in rows
+__global__ void __launch_bounds__(256) audio_stream_emit_kernel(const AudioStreamState st, int32_t* __restrict__ codes_out,
+                                                                 int* __restrict__ n_out, float* __restrict__ pin_out) {
+  const int b = blockIdx.y;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  const int K = st.K, R = st.R, Wf = st.Wf;
+  const int skip = min(max(st.skip[b], 0), Wf);
+  const int take = max(0, min(min(st.take[b], K), Wf - skip));
+  if (i < K * R) {
+    const int k = i / R, r = i - k * R;
+    codes_out[((size_t)b * K + k) * R + r] = k < take ? st.codes[((size_t)b * Wf + skip + k) * R + r] : -1;
+  }
+  if (pin_out) {
+    const int per = st.CD / 4;
+    if (i < K * per) {
+      const int k = i / per, c = (i - k * per) * 4;
+      f32x4s v = {0.f, 0.f, 0.f, 0.f};
+      if (k < take) v = *reinterpret_cast<const f32x4s*>(st.pin + ((size_t)b * Wf + skip + k) * st.CD + c);
+      *reinterpret_cast<f32x4s*>(pin_out + ((size_t)b * K + k) * st.CD + c) = v;
+    }
+  }
+  if (i == 0) {
+    n_out[b] = take;
+    st.M[b] = st.M_next[b];
+    st.C[b] = st.C_next[b];
+    st.closed[b] = st.closed_next[b];
+  }
+}
+
+static bool audio_stream_geometry_ok(const AudioStreamState& st) {
+  return st.sessions >= 1 && st.sessions <= kStreamMaxSessions && st.push >= 1 && st.push <= kAudioStreamMaxPush &&
+         st.halo >= 0 && st.halo <= kStreamMaxFrames && st.R >= 1 && st.geo.hop >= 4 && st.geo.hop % 4 == 0 &&
+         st.Ws >= st.push && st.Ws % st.geo.hop == 0 && st.Wf == st.Ws / st.geo.hop && st.K >= 1 && st.CD >= 0 &&
+         st.CD % 4 == 0 && st.M && st.ring && st.window && st.codes && (st.CD == 0 || st.pin);
+}
+
+hipError_t launch_audio_stream_reset(const AudioStreamState& st, hipStream_t s) {
+  if (!audio_stream_geometry_ok(st)) return hipErrorInvalidValue;
+  return launch_zero_words(st.M, (long long)kAudioStreamCounters * st.sessions, s);  // contiguous arrays
+}
+
+hipError_t launch_audio_stream_plan(const AudioStreamState& st, const int* n_new, const int* flags, hipStream_t s) {
+  if (!audio_stream_geometry_ok(st) || !n_new || !flags) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(audio_stream_plan_kernel, dim3((st.sessions + 255) / 256), dim3(256), 0, s, st, n_new, flags);
+  return hipGetLastError();
+}
+
+hipError_t launch_audio_stream_window(const AudioStreamState& st, const float* new_samples, hipStream_t s) {
+  if (!audio_stream_geometry_ok(st) || !new_samples) return hipErrorInvalidValue;
+  const unsigned gx = (unsigned)((st.Ws / 4 + 255) / 256);
+  hipLaunchKernelGGL(audio_stream_window_kernel, dim3(gx, st.sessions), dim3(256), 0, s, st, new_samples);
+  return hipGetLastError();
+}
+
+hipError_t launch_audio_stream_emit(const AudioStreamState& st, int32_t* codes_out, int* n_out, float* pin_out,
+                                    hipStream_t s) {
+  if (!audio_stream_geometry_ok(st) || !codes_out || !n_out || (pin_out && (!st.pin || (reinterpret_cast<uintptr_t>(pin_out) & 15))))
+    return hipErrorInvalidValue;
+  const long long items = std::max((long long)st.K * st.R, pin_out ? (long long)st.K * (st.CD / 4) : 0LL);
+  hipLaunchKernelGGL(audio_stream_emit_kernel, dim3((unsigned)((items + 255) / 256), st.sessions), dim3(256), 0, s, st,
+                     codes_out, n_out, pin_out);
+  return hipGetLastError();
+}
+
 }  // namespace dcx

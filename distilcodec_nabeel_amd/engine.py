@@ -314,6 +314,47 @@ class NativeCodec:
                                                    ws.numel(), self._stream()))
         return codes, offsets, pin, fup
 
+    def slots_workspace_size(self, batch: int, slot_samples: int) -> int:
+        """Workspace bytes of tokenize_slots for `batch` slots of `slot_samples` samples."""
+        return int(self.L.dcx_ragged_workspace_size(self.h, batch, batch * self.num_frames(slot_samples + 1)))
+
+    def tokenize_slots(self, audio: torch.Tensor, n_samples, want_pjt_in: bool = False, ws: torch.Tensor | None = None,
+                       codes: torch.Tensor | None = None, pjt_in: torch.Tensor | None = None):
+        """audio (B, Ws) raw samples (without the reference's leading zero) with per-slot sample counts
+        `n_samples` -> (codes int32 (B, Wf) ((B, Wf, R) for R > 1 codebooks), x_pjt_in (B, Wf,
+        codebook_dim) | None), Wf = num_frames(Ws + 1) (dcx_tokenize_slots).  Slot b's first
+        num_frames(n_b + 1) rows are what the clip gives alone; codes beyond them are -1, x_pjt_in rows
+        zero; a slot of fewer than 384 samples is dead.  Host lengths are validated (ValueError outside
+        [0, Ws]) and uploaded; a device int32 tensor is used as it stands (a captured graph's lengths
+        buffer; the kernels clamp).  `codes` / `pjt_in`: caller-owned outputs (a captured graph's)."""
+        audio = self._dev(audio, torch.float32)
+        if audio.ndim != 2:
+            raise ValueError(f"audio must be shaped (B, Ws), got {tuple(audio.shape)}")
+        B, Ws = audio.shape
+        if isinstance(n_samples, torch.Tensor) and n_samples.is_cuda:
+            if n_samples.dtype != torch.int32 or n_samples.numel() != B or not n_samples.is_contiguous():
+                raise ValueError(f"device n_samples must be contiguous int32 [{B}]")
+            n_dev = n_samples
+        else:
+            n = np.asarray(n_samples.cpu() if isinstance(n_samples, torch.Tensor) else n_samples, dtype=np.int64).reshape(-1)
+            if n.shape[0] != B or (n < 0).any() or (n > Ws).any():
+                raise ValueError(f"n_samples must hold {B} counts in [0, {Ws}]")
+            n_dev = torch.from_numpy(n.astype(np.int32)).to(self.device)
+        Wf = self.num_frames(Ws + 1)
+        if codes is None:
+            codes = torch.empty(self._codes_shape(B, Wf), dtype=torch.int32, device=self.device)
+        elif tuple(codes.shape) != self._codes_shape(B, Wf) or codes.dtype != torch.int32 or not codes.is_contiguous():
+            raise ValueError(f"codes must be a contiguous int32 tensor shaped {self._codes_shape(B, Wf)}")
+        if pjt_in is None:
+            pjt_in = torch.empty(B, Wf, self.CD, device=self.device) if want_pjt_in else None
+        elif tuple(pjt_in.shape) != (B, Wf, self.CD) or pjt_in.dtype != torch.float32 or not pjt_in.is_contiguous():
+            raise ValueError(f"pjt_in must be a contiguous float32 tensor shaped {(B, Wf, self.CD)}")
+        ws = self._workspace_of(self.slots_workspace_size(B, Ws), ws)
+        with torch.cuda.device(self.device):
+            self._check(self.L.dcx_tokenize_slots(self.h, self._ptr(audio), self._ptr(n_dev), B, Ws, self._ptr(codes),
+                                                  self._ptr(pjt_in), self._ptr(ws), ws.numel(), self._stream()))
+        return codes, pjt_in
+
     def _ragged_lengths(self, lengths, B: int, T: int) -> torch.Tensor:
         """Per-clip frame counts for the ragged decode calls as a device int32 tensor.  A device
         tensor is taken as it stands (a captured graph's lengths buffer; the kernels clamp to
@@ -419,6 +460,75 @@ class NativeCodec:
                                     n_new, flags, ctypes.byref(v[3]), ctypes.byref(v[4]), ctypes.byref(v[5]))
         if rc != _native.DCX_OK:
             raise ValueError("dcx_stream_plan_step: halo_frames must be >= 0 and push_frames >= 1")
+        return tuple(x.value for x in v)
+
+    # ------------------------------------------------------------------ audio streams
+    # Thin wrappers of dcx_stream_encode_*, shaped like the token-stream ones (streaming.AudioStream
+    # owns the tensors and mirrors the slots' counters on the host).
+    def audio_stream_geometry(self, push_samples: int, halo_frames: int) -> tuple[int, int, int]:
+        """(Ws, Wf, K) of a geometry: the window's samples and frames, the rows of a step's outputs."""
+        v = [ctypes.c_int64(0) for _ in range(3)]
+        if self.L.dcx_stream_encode_geometry(self.h, push_samples, halo_frames, *[ctypes.byref(x) for x in v]) != _native.DCX_OK:
+            raise ValueError(f"audio stream: bad geometry (push_samples={push_samples}, halo_frames={halo_frames})")
+        return tuple(x.value for x in v)
+
+    def audio_stream_state_size(self, sessions: int, push_samples: int, halo_frames: int, want_pjt_in: bool = False) -> int:
+        return int(self.L.dcx_stream_encode_state_size(self.h, sessions, push_samples, halo_frames, int(want_pjt_in)))
+
+    def audio_stream_state(self, sessions: int, push_samples: int, halo_frames: int, want_pjt_in: bool = False) -> torch.Tensor:
+        """A reset state buffer for `sessions` slots (dcx_stream_encode_state_size, dcx_stream_encode_reset)."""
+        need = self.audio_stream_state_size(sessions, push_samples, halo_frames, want_pjt_in)
+        if need == 0:
+            raise ValueError(f"audio stream: bad geometry (sessions={sessions}, push_samples={push_samples}, "
+                             f"halo_frames={halo_frames})")
+        state = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self.audio_stream_reset(state, sessions, push_samples, halo_frames, want_pjt_in)
+        return state
+
+    def audio_stream_reset(self, state: torch.Tensor, sessions: int, push_samples: int, halo_frames: int,
+                           want_pjt_in: bool = False) -> None:
+        with torch.cuda.device(self.device):
+            self._check(self.L.dcx_stream_encode_reset(self.h, self._ptr(state), state.numel(), sessions, push_samples,
+                                                       halo_frames, int(want_pjt_in), self._stream()))
+
+    def audio_stream_workspace_size(self, sessions: int, push_samples: int, halo_frames: int) -> int:
+        Ws, _, _ = self.audio_stream_geometry(push_samples, halo_frames)
+        return self.slots_workspace_size(sessions, Ws)
+
+    def audio_stream_step(self, state: torch.Tensor, sessions: int, push_samples: int, halo_frames: int,
+                          new_samples: torch.Tensor, n_new: torch.Tensor, flags: torch.Tensor, codes_out: torch.Tensor,
+                          n_out: torch.Tensor, pjt_in_out: torch.Tensor | None = None, ws: torch.Tensor | None = None) -> None:
+        """One step of every slot (dcx_stream_encode_step) on the caller's device tensors: new_samples
+        fp32 (sessions, push_samples), n_new / flags / n_out int32 (sessions,), codes_out int32
+        (sessions, K(, R)), pjt_in_out fp32 (sessions, K, codebook_dim) or None."""
+        B, P, h = sessions, push_samples, halo_frames
+        K = self.audio_stream_geometry(P, h)[2]
+        want = {"new_samples": (new_samples, torch.float32, (B, P)), "n_new": (n_new, torch.int32, (B,)),
+                "flags": (flags, torch.int32, (B,)), "n_out": (n_out, torch.int32, (B,)),
+                "codes_out": (codes_out, torch.int32, self._codes_shape(B, K))}
+        if pjt_in_out is not None:
+            want["pjt_in_out"] = (pjt_in_out, torch.float32, (B, K, self.CD))
+        for name, (t, dtype, shape) in want.items():
+            if t.device != self.device or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {dtype} tensor shaped {shape} on {self.device}")
+        if ws is None:
+            ws = self._workspace_of(self.audio_stream_workspace_size(B, P, h), None)
+        elif ws.device != self.device or ws.dtype != torch.uint8 or not ws.is_contiguous():
+            raise ValueError(f"workspace must be a contiguous uint8 tensor on {self.device}")
+        with torch.cuda.device(self.device):  # the call itself checks the sizes of state and ws
+            self._check(self.L.dcx_stream_encode_step(self.h, self._ptr(state), state.numel(), B, P, h, self._ptr(new_samples),
+                                                      self._ptr(n_new), self._ptr(flags), self._ptr(codes_out),
+                                                      self._ptr(n_out), self._ptr(pjt_in_out), self._ptr(ws), ws.numel(),
+                                                      self._stream()))
+
+    def audio_stream_plan_step(self, halo_frames: int, push_samples: int, M: int, C: int, closed: int, n_new: int, flags: int):
+        """dcx_stream_encode_plan_step (host only): (M, C, closed, len, start, skip, take) after one step
+        of a slot."""
+        v = [ctypes.c_int32(x) for x in (M, C, closed, 0, 0, 0, 0)]
+        rc = self.L.dcx_stream_encode_plan_step(self.h, halo_frames, push_samples, ctypes.byref(v[0]), ctypes.byref(v[1]),
+                                                ctypes.byref(v[2]), n_new, flags, *[ctypes.byref(x) for x in v[3:]])
+        if rc != _native.DCX_OK:
+            raise ValueError("dcx_stream_encode_plan_step: halo_frames must be >= 0 and push_samples >= 1")
         return tuple(x.value for x in v)
 
     def module_io(self, name: str) -> tuple[int, int, int]:

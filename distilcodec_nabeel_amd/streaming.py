@@ -6,7 +6,8 @@ decoded on its own, exactly as the reference does for a 1 s clip
 (`DistilCodec.encode` + `decode_from_codes`, distil_codec.py:545-594). `HaloStream` below is the
 halo-overlapped variant whose chunked output equals the full-clip output.
 `TokenStream` is the other direction for many sessions at once: codes -> audio while the codes are
-still arriving, one dcx_stream_decode_step per push (DESIGN.md §3 "Token streams").
+still arriving, one dcx_stream_decode_step per push (DESIGN.md §3 "Token streams"); `AudioStream` is
+its mirror, audio -> codes for many sessions, one dcx_stream_encode_step per push ("Audio streams").
 
 The C-ABI stage calls allocate nothing and never synchronise (include/distilcodec_amd.h), so a
 whole `dcx_encode_decode` call is captured by `torch.cuda.graph` as it is launched: every kernel
@@ -87,7 +88,71 @@ def receptive_field(cfg: dict) -> tuple[int, int]:
     return int(e), int(math.ceil(d))
 
 
-class TokenStream:
+class _SlotStream:
+    """What TokenStream and AudioStream share: the step's inputs (a payload of 32-bit words, then the
+    slots' counts and flags) as views of one device buffer, staged through a few pinned host buffers
+    in turn and uploaded in one copy, so a push never waits for the device; and the step run eagerly
+    or as one captured HIP graph over the stream's static tensors.  A subclass provides `_step()`
+    (the native step on its tensors) and `_reset()` (its state emptied)."""
+
+    FINAL, RESTART = 1, 2
+
+    def _init_io(self, n_words: int):
+        B, dev = self.sessions, self.engine.device
+        self._n_words = n_words
+        self._in = torch.zeros(n_words + 2 * B, dtype=torch.int32, device=dev)
+        # (each host buffer is reused once its own upload has run)
+        self._hosts = [torch.zeros(n_words + 2 * B, dtype=torch.int32).pin_memory() for _ in range(4)]
+        self._uploaded = [None] * len(self._hosts)
+        self._turn = 0
+        self.n_new, self.flags = self._in[n_words:n_words + B], self._in[n_words + B:]
+        self.graph = None
+
+    def _capture(self):
+        dev = self.engine.device
+        with torch.cuda.device(dev):
+            s = torch.cuda.Stream(dev)  # eager warm-up (first-launch work) off the capture
+            s.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(s):
+                self._step()  # every slot pushes nothing: the counters stay 0
+                self._reset()
+            torch.cuda.current_stream(dev).wait_stream(s)
+            self.graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self.graph):
+                self._step()
+
+    def _flags_of(self, n_entries: int, final, restart) -> list:
+        B = self.sessions
+        if n_entries != B:
+            raise ValueError(f"expected one entry per slot ({B}), got {n_entries}")
+        final, restart = set(final), set(restart)
+        if not (final | restart) <= set(range(B)):
+            raise ValueError(f"final / restart name slots outside [0, {B})")
+        return [(self.FINAL if b in final else 0) | (self.RESTART if b in restart else 0) for b in range(B)]
+
+    def _upload_and_run(self, payload, counts, flags):
+        """payload: the step's int32 words (a flat numpy view), staged with counts and flags, uploaded
+        in one copy; then the step."""
+        B, n = self.sessions, self._n_words
+        k = self._turn
+        self._turn = (k + 1) % len(self._hosts)
+        if self._uploaded[k] is not None:
+            self._uploaded[k].synchronize()  # the upload of four pushes ago
+        host = self._hosts[k].numpy()
+        host[:n] = payload
+        host[n:n + B] = counts
+        host[n + B:] = flags
+        with torch.cuda.device(self.engine.device):
+            self._in.copy_(self._hosts[k], non_blocking=True)
+            self._uploaded[k] = torch.cuda.Event()
+            self._uploaded[k].record()
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            self._step()
+
+
+class TokenStream(_SlotStream):
     """Batched streaming decode, codes -> audio (DESIGN.md §3 "Token streams"): `sessions` utterances
     that each grow by at most `push_frames` frames per `push`, decoded together in one
     dcx_stream_decode_step per push, every slot's samples those of its full-clip decode up to fp32
@@ -101,7 +166,6 @@ class TokenStream:
     outside the codebook; it stays 0 after the host-side validation `push` does.
     """
 
-    FINAL, RESTART = 1, 2
     UNUSED = 1 << 20  # fills the entries of new_codes beyond a slot's count: never read
 
     def __init__(self, engine: NativeCodec, sessions: int, push_frames: int, halo_frames: int | None = None,
@@ -112,36 +176,23 @@ class TokenStream:
         self.token_id_offset = token_id_offset
         B, P, h, R, dev = self.sessions, self.push_frames, self.halo_frames, engine.R, engine.device
         self.state = engine.stream_state(B, P, h)  # ValueError for a bad geometry
-        # the step's inputs as views of one buffer, uploaded in one copy from pinned memory
         n_codes = B * P * R
-        self._in = torch.zeros(n_codes + 2 * B, dtype=torch.int32, device=dev)
-        # (a few host buffers in turn, each reused once its own upload has run: push does not wait for the device)
-        self._hosts = [torch.zeros(n_codes + 2 * B, dtype=torch.int32).pin_memory() for _ in range(4)]
-        self._uploaded = [None] * len(self._hosts)
-        self._turn = 0
+        self._init_io(n_codes)
         self.new_codes = self._in[:n_codes].view(engine._codes_shape(B, P))
-        self.n_new, self.flags = self._in[n_codes:n_codes + B], self._in[n_codes + B:]
         self.wav_out = torch.zeros(B, engine.hop * (P + h), device=dev)
         self.n_out = torch.zeros(B, dtype=torch.int32, device=dev)
         self.n_invalid = torch.zeros(1, dtype=torch.int32, device=dev)
         self.ws = torch.empty(engine.workspace_size(B, P + 2 * h), dtype=torch.uint8, device=dev)
         self._slots = [(0, 0, 0)] * B  # host mirror of (T, E, closed)
-        self.graph = None
         if graph:
-            with torch.cuda.device(dev):
-                s = torch.cuda.Stream(dev)  # eager warm-up (first-launch work) off the capture
-                s.wait_stream(torch.cuda.current_stream(dev))
-                with torch.cuda.stream(s):
-                    self._step()  # every slot pushes nothing: the counters stay 0
-                    engine.stream_reset(self.state, B, P, h)
-                torch.cuda.current_stream(dev).wait_stream(s)
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph):
-                    self._step()
+            self._capture()
 
     def _step(self):
         self.engine.stream_step(self.state, self.sessions, self.push_frames, self.halo_frames, self.new_codes, self.n_new,
                                 self.flags, self.wav_out, self.n_out, self.n_invalid, ws=self.ws)
+
+    def _reset(self):
+        self.engine.stream_reset(self.state, self.sessions, self.push_frames, self.halo_frames)
 
     def slot(self, b: int) -> tuple[int, int, bool]:
         """(codes received, frames emitted, closed) of slot b, from the host mirror."""
@@ -158,15 +209,10 @@ class TokenStream:
         import numpy as np
 
         eng, B, P, R = self.engine, self.sessions, self.push_frames, self.engine.R
-        if len(codes_per_slot) != B:
-            raise ValueError(f"expected one entry per slot ({B}), got {len(codes_per_slot)}")
-        final, restart = set(final), set(restart)
-        if not (final | restart) <= set(range(B)):
-            raise ValueError(f"final / restart name slots outside [0, {B})")
+        flags = self._flags_of(len(codes_per_slot), final, restart)
         stage = np.full((B, P, R), self.UNUSED, dtype=np.int32)
-        counts, flags = [0] * B, [0] * B
+        counts = [0] * B
         for b, c in enumerate(codes_per_slot):
-            flags[b] = (self.FINAL if b in final else 0) | (self.RESTART if b in restart else 0)
             if c is None:
                 continue
             c = np.asarray(c.cpu() if isinstance(c, torch.Tensor) else c)
@@ -177,28 +223,13 @@ class TokenStream:
             n = c.shape[0]
             if n > P:
                 raise ValueError(f"slot {b}: {n} frames exceed push_frames={P}")
-            if n and self._slots[b][2] and b not in restart:
+            if n and self._slots[b][2] and not flags[b] & self.RESTART:
                 raise RuntimeError(f"slot {b} is closed: pass it in `restart` to start a new utterance")
             if n and (int(c.min()) < 0 or int(c.max()) >= eng.NC):
                 raise IndexError(f"slot {b}: audio code out of range for a codebook of {eng.NC} entries")
             stage[b, :n] = c
             counts[b] = n
-        k = self._turn
-        self._turn = (k + 1) % len(self._hosts)
-        if self._uploaded[k] is not None:
-            self._uploaded[k].synchronize()  # the upload of four pushes ago
-        host = self._hosts[k].numpy()
-        host[:B * P * R] = stage.reshape(-1)
-        host[B * P * R:B * P * R + B] = counts
-        host[B * P * R + B:] = flags
-        with torch.cuda.device(eng.device):
-            self._in.copy_(self._hosts[k], non_blocking=True)
-            self._uploaded[k] = torch.cuda.Event()
-            self._uploaded[k].record()
-        if self.graph is not None:
-            self.graph.replay()
-        else:
-            self._step()
+        self._upload_and_run(stage.reshape(-1), counts, flags)
         out = self.wav_out.clone()  # the static output is overwritten by the next push
         outs = []
         for b in range(B):
@@ -224,6 +255,110 @@ class TokenStream:
                 raise ValueError(f"slot {b}: a code list of {a.size} entries is not a multiple of the {R} codebooks per frame")
             codes.append((a - off).reshape(-1, R))
         return [w[None, None, :] for w in self.push(codes, final=final, restart=restart)]
+
+
+class AudioStream(_SlotStream):
+    """Batched streaming tokenization, audio -> codes (DESIGN.md §3 "Audio streams"), the mirror of
+    TokenStream: `sessions` utterances that each grow by at most `push_samples` raw samples per `push`,
+    tokenized together in one dcx_stream_encode_step per push, every slot's codes those of its full
+    clip (`tokenize_ragged` of the clip alone) up to fp32 summation order.  A frame's code is returned
+    once `halo_frames` mel frames after it exist that touch no reflected sample (default: the encoder's
+    half receptive field, `receptive_field(cfg)[0]`), or when the slot is marked `final`, where the
+    window ends at the utterance's true last sample.  The slots' state lives on the device and their
+    counters are mirrored on the host (dcx_stream_encode_plan_step), so `push` reads nothing back.
+
+    `graph=True` captures the step once in a HIP graph and replays it per push, bit-equal to the eager
+    step.  `want_pjt_in`: every push also leaves the emitted frames' x_pjt_in rows in `pjt_in_out`.
+    """
+
+    MIN_SAMPLES = 384  # an utterance needs the reflect pad's length
+
+    def __init__(self, engine: NativeCodec, sessions: int, push_samples: int, halo_frames: int | None = None,
+                 graph: bool = False, want_pjt_in: bool = False, token_id_offset: int = 0, token_table: dict | None = None):
+        self.engine = engine
+        self.token_table = token_table  # tokens.construct_audio_code's table (push_tokens)
+        self.sessions, self.push_samples = int(sessions), int(push_samples)
+        self.halo_frames = receptive_field(engine.cfg)[0] if halo_frames is None else int(halo_frames)
+        self.want_pjt_in = bool(want_pjt_in)
+        self.token_id_offset = token_id_offset
+        B, P, h, dev = self.sessions, self.push_samples, self.halo_frames, engine.device
+        self.state = engine.audio_stream_state(B, P, h, self.want_pjt_in)  # ValueError for a bad geometry
+        self.window_samples, self.window_frames, self.out_frames = engine.audio_stream_geometry(P, h)
+        self._init_io(B * P)
+        self.new_samples = self._in[:B * P].view(torch.float32).view(B, P)
+        self.codes_out = torch.full(engine._codes_shape(B, self.out_frames), -1, dtype=torch.int32, device=dev)
+        self.n_out = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.pjt_in_out = torch.zeros(B, self.out_frames, engine.CD, device=dev) if self.want_pjt_in else None
+        self.ws = torch.empty(engine.audio_stream_workspace_size(B, P, h), dtype=torch.uint8, device=dev)
+        self._slots = [(0, 0, 0)] * B  # host mirror of (M, C, closed)
+        if graph:
+            self._capture()
+
+    def _step(self):
+        self.engine.audio_stream_step(self.state, self.sessions, self.push_samples, self.halo_frames, self.new_samples,
+                                      self.n_new, self.flags, self.codes_out, self.n_out, self.pjt_in_out, ws=self.ws)
+
+    def _reset(self):
+        self.engine.audio_stream_reset(self.state, self.sessions, self.push_samples, self.halo_frames, self.want_pjt_in)
+
+    def slot(self, b: int) -> tuple[int, int, bool]:
+        """(samples received, codes emitted, closed) of slot b, from the host mirror."""
+        M, C, closed = self._slots[b]
+        return M, C, bool(closed)
+
+    def push(self, chunks_per_slot, final=(), restart=()) -> list:
+        """One step.  `chunks_per_slot`: per slot, None or the new raw samples (1-D, at most
+        push_samples); `final` / `restart`: the slots that end with this push / start a new utterance
+        with it.  Returns one int32 tensor [take] ([take, R] for R > 1 codebooks) per slot: the codes
+        that became final.  ValueError for a chunk above push_samples or a `final` that would leave
+        an utterance of fewer than 384 samples, RuntimeError for samples pushed to a closed slot
+        without `restart`: all before any upload, so a refused push changes nothing."""
+        import numpy as np
+
+        eng, B, P = self.engine, self.sessions, self.push_samples
+        flags = self._flags_of(len(chunks_per_slot), final, restart)
+        stage = np.full((B, P), np.nan, dtype=np.float32)  # entries beyond a slot's count: never read
+        counts = [0] * B
+        for b, c in enumerate(chunks_per_slot):
+            if c is not None:
+                c = np.asarray(c.cpu() if isinstance(c, torch.Tensor) else c, dtype=np.float32).reshape(-1)
+                n = c.shape[0]
+                if n > P:
+                    raise ValueError(f"slot {b}: a chunk of {n} samples exceeds push_samples={P}")
+                if n and self._slots[b][2] and not flags[b] & self.RESTART:
+                    raise RuntimeError(f"slot {b} is closed: pass it in `restart` to start a new utterance")
+                stage[b, :n] = c
+                counts[b] = n
+            M, _, closed = (0, 0, 0) if flags[b] & self.RESTART else self._slots[b]
+            if flags[b] & self.FINAL and not closed and M + counts[b] < self.MIN_SAMPLES:
+                raise ValueError(f"slot {b}: final on an utterance of {M + counts[b]} samples, fewer than the "
+                                 f"{self.MIN_SAMPLES} the reflect pad needs")
+        self._upload_and_run(stage.reshape(-1).view(np.int32), counts, flags)
+        out = self.codes_out.clone()  # the static output is overwritten by the next push
+        outs = []
+        for b in range(B):
+            M, C, closed, _, _, _, take = eng.audio_stream_plan_step(self.halo_frames, P, *self._slots[b], counts[b], flags[b])
+            self._slots[b] = (M, C, closed)
+            outs.append(out[b, :take])
+        return outs
+
+    def push_tokens(self, chunks_per_slot, final=(), restart=(), add_token_offset: bool = True) -> list:
+        """`push`, returning per slot the flat frame-major LLM token ids `DistilCodec.encode` yields
+        for the emitted frames (R ids per frame): the `absolute_token_id` of tokens.audio_tokenize with
+        the stream's token table, or the codes plus `token_id_offset` without one; the ids
+        `TokenStream.push_tokens` takes.  `add_token_offset=False`: the codes themselves."""
+        from . import tokens
+
+        outs = []
+        for c in self.push(chunks_per_slot, final=final, restart=restart):
+            flat = c.reshape(-1).tolist()
+            if not add_token_offset:
+                outs.append(flat)
+            elif self.token_table is not None:
+                outs.append([t["absolute_token_id"] for t in tokens.audio_tokenize(self.token_table, flat, 1, self.engine.R)])
+            else:
+                outs.append([x + self.token_id_offset for x in flat])
+        return outs
 
 
 class HaloStream:

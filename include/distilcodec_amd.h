@@ -186,6 +186,29 @@ int dcx_tokenize_ragged(dcx_codec* h, const float* audio_packed, const int32_t* 
                         int32_t batch, int64_t total_samples, int64_t total_frames, int32_t* codes, float* x_pjt_in,
                         float* quantized_fup, void* workspace, size_t ws_bytes, void* stream);
 
+/* Slot tokenization: the ragged contract in the padded layout, with the per-slot sample counts in DEVICE
+ * memory, so one hipGraph captured for (batch, slot_samples) serves any lengths (the encoder-side mirror
+ * of dcx_decode_ragged).  audio [batch][slot_samples] raw samples (the reference's leading zero is applied
+ * by the framing kernel, as in dcx_tokenize_ragged); n_samples_dev int32 [batch], clamped by the kernels
+ * to [0, slot_samples]; Wf = dcx_num_frames(slot_samples + 1); with T_b = dcx_num_frames(n_b + 1), or 0 for
+ * n_b < 384 (a dead slot: the reflect pad needs n_b + 1 > 384):
+ *   codes[b][0 : T_b][R], x_pjt_in[b][0 : T_b]     what the clip gives ALONE (dcx_tokenize_ragged's rows);
+ *   codes[b][T_b : Wf] = -1, x_pjt_in[b][T_b : Wf] = 0   (x_pjt_in [batch][Wf][codebook_dim] may be NULL).
+ * Samples at or beyond n_b and whatever the workspace held are never read into any result, range
+ * shift or range flag.  The arithmetic is dcx_tokenize_ragged's (whole-frame one-tap DFT, unfolded stem,
+ * fixed tiles, the same dwconv_ln row arithmetic); its three clip-aware kernels take each slot's length
+ * from n_samples_dev, write the rows beyond it as zeros, and leave before their loads where a tile or
+ * run lies wholly beyond it; the row-wise steps run on all batch * Wf rows.  Kernel families, tiles and
+ * run widths follow (batch, Wf) alone, never the lengths.  Workspace: dcx_ragged_workspace_size(h, batch,
+ * batch * Wf).  Stream-ordered, allocates nothing, never synchronises, capturable, and runs on the
+ * caller's stream alone.  Refused before the first launch, with the reason in dcx_last_error:
+ * DCX_GEMM_F32 (DCX_ERR_INVALID_ARG), split-K on (DCX_ERR_STATE), a short workspace
+ * (DCX_ERR_WORKSPACE), slot_samples < 384 or more than 2^31 - 1 samples / 2^20 frames in all
+ * (DCX_ERR_INVALID_ARG). */
+int dcx_tokenize_slots(dcx_codec* h, const float* audio, const int32_t* n_samples_dev, int32_t batch,
+                       int64_t slot_samples, int32_t* codes, float* x_pjt_in, void* workspace, size_t ws_bytes,
+                       void* stream);
+
 /* Ragged decode: codes (or z) of clips of different lengths -> waveforms, every clip's samples what
  * dcx_vq_decode -> dcx_generate give for that clip ALONE.  (The padded calls reproduce the reference,
  * which pads a batch of code lists to the longest with code 0: the generator is conv-only, so there
@@ -251,6 +274,63 @@ int dcx_stream_decode_step(dcx_codec* h, void* state, size_t state_bytes, int32_
                            void* workspace, size_t ws_bytes, void* stream);
 int dcx_stream_plan_step(int32_t halo_frames, int32_t push_frames, int32_t* T, int32_t* E, int32_t* closed,
                          int32_t n_new, int32_t flags, int32_t* len, int32_t* skip, int32_t* take);
+
+/* Audio streams: batched streaming tokenization, audio -> codes, the mirror of the token streams, for
+ * `sessions` utterances that each grow by at most push_samples raw samples per step.  Every step returns
+ * the codes that became final, and an utterance's codes together are those of its full clip
+ * (dcx_tokenize_ragged of the clip alone) up to fp32 summation order: a frame is final once
+ * halo_frames mel frames after it exist that touch no reflected sample, or at FINAL; the encoder's half
+ * receptive field is 60 frames for the published model.
+ * A slot holds M (raw samples received), C (codes emitted), closed, and the samples from
+ * 256 max(0, C - h - 2) on.  avail(M) = M >= 639 ? (M - 639) / 256 + 1 : 0 (the frames that touch no
+ * sample reflected at the end).  One step, per slot b, with n = n_new_dev[b] clamped to [0, push_samples]
+ * and flags_dev[b] (DCX_STREAM_FINAL / DCX_STREAM_RESTART):
+ *   1. RESTART: M = C = 0, closed = 0.                   2. closed: n = 0 (the new samples are ignored).
+ *   3. M += n; a = max(0, C - h - 2); c_new = FINAL ? dcx_num_frames(M + 1) (0 for M < 384)
+ *      : max(C, avail(M) - h).
+ *   4. the window is raw samples [256 a, M), len = M - 256 a, tokenized as dcx_tokenize_slots
+ *      tokenizes a slot of len samples: a clip alone.  Its leading zero is the utterance's own while
+ *      a = 0; later it displaces one sample that only window frames 0-1 read, inside the 2-frame margin
+ *      that also absorbs the left reflect pad.  At FINAL the window ends at the utterance's last sample,
+ *      so the reflect pad and the convs' zero padding there are the full clip's.
+ *   5. window frames [C - a, c_new - a) are emitted, take = c_new - C; a step with take = 0 runs its slot
+ *      with length 0 (dead: its tiles are skipped).       6. C = c_new; FINAL sets closed.
+ * A FINAL on an utterance of fewer than 384 samples emits nothing and closes.  Bounds (each reached):
+ *   len <= push_samples + 256 (2 h + 2) + 638;  Ws = that bound rounded up to a multiple of 256, Wf = Ws / 256;
+ *   take <= ceil(push_samples / 256) without FINAL;  take <= K = h + (push_samples + 639) / 256 at FINAL;
+ *   M - 256 C <= 256 h + 638 after any step.
+ *   codes_out[b][0 : take][R]   the emitted codes;  codes_out[b][take : K] = -1;  n_out_dev[b] = take;
+ *   x_pjt_in_out[b][0 : take]   (optional, [sessions][K][codebook_dim], 16-byte aligned) their x_pjt_in rows,
+ *                               zeros behind them.
+ * new_samples [sessions][push_samples] (entries at or beyond n are never read), n_new_dev, flags_dev,
+ * codes_out [sessions][K][R] and n_out_dev are DEVICE memory, so one hipGraph captured for a geometry
+ * serves every step.  All state lives in the caller's device buffer `state` (16-byte aligned,
+ * dcx_stream_encode_state_size bytes, 0 for bad arguments; want_pjt_in != 0 adds the x_pjt_in window a
+ * step with x_pjt_in_out needs), which dcx_stream_encode_reset empties; workspace:
+ * dcx_ragged_workspace_size(h, sessions, sessions * Wf).  dcx_stream_encode_geometry: Ws, Wf and K of a
+ * geometry (host only).  Every call takes the same geometry.  Stream-ordered, allocates nothing, never
+ * synchronises, capturable, one chain on the caller's stream.  The slots' counters are committed by
+ * the step's last kernel: a step that returns an error leaves every slot as it was.
+ * dcx_stream_encode_plan_step (host only, no HIP call; the handle is read for the STFT framing): the same
+ * arithmetic on one slot's counters, so a caller mirrors M / C / closed and knows every take without
+ * reading device memory back; start = 256 a, skip = C - a.
+ * DCX_ERR_INVALID_ARG: sessions < 1 (> 65535), push_samples < 1 (> 2^24), halo_frames < 0 (> 65536),
+ * windows beyond 2^31 - 1 samples or 2^20 frames in all, a null or short state buffer; and whatever
+ * dcx_tokenize_slots refuses, with its status, before the first launch (DCX_GEMM_F32:
+ * DCX_ERR_INVALID_ARG; split-K: DCX_ERR_STATE; a short workspace: DCX_ERR_WORKSPACE). */
+size_t dcx_stream_encode_state_size(const dcx_codec* h, int32_t sessions, int32_t push_samples, int32_t halo_frames,
+                                    int32_t want_pjt_in);
+int dcx_stream_encode_geometry(const dcx_codec* h, int32_t push_samples, int32_t halo_frames, int64_t* window_samples,
+                               int64_t* window_frames, int64_t* out_frames);
+int dcx_stream_encode_reset(dcx_codec* h, void* state, size_t state_bytes, int32_t sessions, int32_t push_samples,
+                            int32_t halo_frames, int32_t want_pjt_in, void* stream);
+int dcx_stream_encode_step(dcx_codec* h, void* state, size_t state_bytes, int32_t sessions, int32_t push_samples,
+                           int32_t halo_frames, const float* new_samples, const int32_t* n_new_dev,
+                           const int32_t* flags_dev, int32_t* codes_out, int32_t* n_out_dev, float* x_pjt_in_out,
+                           void* workspace, size_t ws_bytes, void* stream);
+int dcx_stream_encode_plan_step(const dcx_codec* h, int32_t halo_frames, int32_t push_samples, int32_t* M, int32_t* C,
+                                int32_t* closed, int32_t n_new, int32_t flags, int32_t* len, int32_t* start,
+                                int32_t* skip, int32_t* take);
 
 /* Sample-rate conversion by up/down for input audio at another rate (replaces librosa.resample,
  * distil_codec.py:108-110 and :676, and librosa.load(sr=...) in meldataset.py:18-20).  Polyphase FIR
