@@ -297,10 +297,21 @@ __device__ __forceinline__ void epilogue_form(const ConvParams& p, const ConvPar
       float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, __builtin_ldexpf(1.0f, h2o && !h2row ? pre.osh : 0))));
   float vmax = 0.f;
   const int lq_live = RAG ? clip_rows(pr.clip_len, pr.len_mul, b, p.Lq) : p.Lq;
-  constexpr int G = 8, NH = 2;
-  static_assert(NT % (BN / G) == 0, "each thread keeps one channel group");
+  // Line-major lanes (dcx_epi_lines.h): a thread owns 4 consecutive channels of a row and twice the
+  // rows that epilogue_lds's 8-channel groups give it, so every 16-byte-per-lane load and store of a
+  // wave moves whole contiguous 128-byte lines, and the LDS staging reads are one f32x4 per row, 64
+  // lanes x 16 B contiguous (a 16-lane group reads 256 contiguous bytes: 16 distinct bank quads).
+  // Two forms keep epilogue_lds's 8-channel groups (NH = 2 pieces per row, 16 B apart, read from LDS
+  // in the order hsw): the one-tap forms (RROW != 0), whose per-row range words and scales are per
+  // thread and row and double with the rows (conv_gemm_x3dw<256,256> 26.7 -> 27.3 ms per C2 step with
+  // 4-channel groups), and the ragged 256-column forms with a residual and outputs of their own
+  // (EpiC2, last of mean), which gained 8 / 36 / 32 bytes of scratch with them
+  // (profiles/epi_lines_resources.md).
+  constexpr bool LINES = RROW == 0 && !(RAG && BN == 256 && need_r && (F::mean == MEAN_NONE || F::mean == MEAN_LAST));
+  constexpr int G = LINES ? kEpiG : 8, NH = G / 4;
+  static_assert(NT % (BN / G) == 0 && LDSW == epi_ldsw(BN), "each thread keeps one channel group");
   const int cg = (tid % (BN / G)) * G, trow = tid / (BN / G), co = co0 + cg;
-  const int hsw = (lane >> 3) & 1;  // LDS read order of the two halves (epilogue_lds)
+  const int hsw = (lane >> 3) & 1;  // NH = 2: LDS read order of the two halves (epilogue_lds)
   f32x4 bias4[NH], gamma4[NH];
 #pragma unroll
   for (int h = 0; h < NH; ++h) {
@@ -308,16 +319,16 @@ __device__ __forceinline__ void epilogue_form(const ConvParams& p, const ConvPar
     gamma4[h] = F::epi == EPI_GAMMA_RES ? *reinterpret_cast<const f32x4*>(p.gamma + co + 4 * h) : f32x4{0.f, 0.f, 0.f, 0.f};
   }
   constexpr int RSTEP = NT / (BN / G), ROWS_T = RPP / RSTEP;
-  static_assert(RPP % RSTEP == 0, "epilogue rows per thread");
+  static_assert(RPP % RSTEP == 0 && (!LINES || RSTEP == epi_rstep(NT, BN)), "epilogue rows per thread");
   constexpr auto div_cap = [](int n, int cap) {
     int d = n < cap ? n : cap;
     while (n % d) --d;
     return d;
   };
-  // batches of 4 rows, 2 where residual / mean rows are loaded (16-byte loads, 8 VGPRs per row and
-  // tensor): two batches' rows are in registers at a time here, and with 4 the 256 x 256 residual
-  // forms spilled 52-176 bytes, reloaded inside the row code.  (EpiPw1's per-row range words, rin /
-  // rbnd, are one VGPR each: it keeps 4.)
+  // batches of 8 16-byte pieces per thread, 4 where residual / mean rows are loaded (4 VGPRs per piece
+  // and tensor): two batches' rows are in registers at a time here, and with twice as many the
+  // 256 x 256 residual forms spilled 52-176 bytes, reloaded inside the row code.  (EpiPw1's per-row
+  // range words, rin / rbnd, are one VGPR each: it keeps 4 rows.)
   constexpr int IB = div_cap(ROWS_T, need_r || need_m ? 4 / NH : 8 / NH);
   auto row_bound = [&](int q) { return fmaf(pr.yb.g[0], fmaxf(pr.yb.m[0][(long long)b * p.Lq + q], pr.yb.f[0]), pr.yb.c); };
 
@@ -365,10 +376,14 @@ __device__ __forceinline__ void epilogue_form(const ConvParams& p, const ConvPar
         const int q = q0 + r0 + rl;
         const bool dead = RAG && q >= lq_live;  // beyond the clip's length (its own zero padding)
         const float rin_ = RIN ? rin[RIN ? k : 0] : 1.0f;
-        const f32x4 u = *reinterpret_cast<const f32x4*>(smem + rl * LDSW + cg + 4 * hsw);
-        const f32x4 v = *reinterpret_cast<const f32x4*>(smem + rl * LDSW + cg + 4 * (1 - hsw));
-        x[k][0] = (hsw ? v : u) * rin_ + bias4[0];
-        x[k][1] = (hsw ? u : v) * rin_ + bias4[1];
+        if constexpr (LINES) {  // one piece per row: the 64 lanes read 1 KiB (two runs of 512 B) of the staged rows
+          x[k][0] = *reinterpret_cast<const f32x4*>(smem + epi_lds_float(rl, tid, BN)) * rin_ + bias4[0];
+        } else {
+          const f32x4 u = *reinterpret_cast<const f32x4*>(smem + rl * LDSW + cg + 4 * hsw);
+          const f32x4 v = *reinterpret_cast<const f32x4*>(smem + rl * LDSW + cg + 4 * (1 - hsw));
+          x[k][0] = (hsw ? v : u) * rin_ + bias4[0];
+          x[k][NH - 1] = (hsw ? u : v) * rin_ + bias4[NH - 1];
+        }
 #pragma unroll
         for (int h = 0; h < NH; ++h) {
           if constexpr (F::epi == EPI_GELU) {
@@ -425,19 +440,30 @@ __device__ __forceinline__ void epilogue_form(const ConvParams& p, const ConvPar
 #pragma unroll
           for (int h = 0; h < NH; ++h) *reinterpret_cast<f32x4*>(p.y + o + 4 * h) = x[k][h];
         }
-        float xv[8];
+        if constexpr (LINES) {  // (the lanes of an h2 pair own the same row, so both are here or neither)
+          if constexpr (F::y6h) store_h2_pair<false>(y6, orow, p.Cout, co, x[k][0], sc);
+          if constexpr (F::y2 || F::y6sh) {
+            f32x4 sv;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) xv[e] = x[k][e >> 2][e & 3];
-        if constexpr (F::y6h) store_h2_8<false>(y6, orow, p.Cout, co, xv, sc);
-        if constexpr (F::y2 || F::y6sh) {
-          float sv[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) sv[e] = silu_f(xv[e]);
-          if constexpr (F::y2) {
-            *reinterpret_cast<f32x4*>(p.y2 + o) = f32x4{sv[0], sv[1], sv[2], sv[3]};
-            *reinterpret_cast<f32x4*>(p.y2 + o + 4) = f32x4{sv[4], sv[5], sv[6], sv[7]};
+            for (int e = 0; e < 4; ++e) sv[e] = silu_f(x[k][0][e]);
+            if constexpr (F::y2) *reinterpret_cast<f32x4*>(p.y2 + o) = sv;
+            if constexpr (F::y6sh) store_h2_pair<false>(y6s, orow, p.Cout, co, sv, sc);
           }
-          if constexpr (F::y6sh) store_h2_8<false>(y6s, orow, p.Cout, co, sv, sc);
+        } else {
+          float xv[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) xv[e] = x[k][e >> 2][e & 3];
+          if constexpr (F::y6h) store_h2_8<false>(y6, orow, p.Cout, co, xv, sc);
+          if constexpr (F::y2 || F::y6sh) {
+            float sv[8];
+#pragma unroll
+            for (int e = 0; e < 8; ++e) sv[e] = silu_f(xv[e]);
+            if constexpr (F::y2) {
+              *reinterpret_cast<f32x4*>(p.y2 + o) = f32x4{sv[0], sv[1], sv[2], sv[3]};
+              *reinterpret_cast<f32x4*>(p.y2 + o + 4) = f32x4{sv[4], sv[5], sv[6], sv[7]};
+            }
+            if constexpr (F::y6sh) store_h2_8<false>(y6s, orow, p.Cout, co, sv, sc);
+          }
         }
       }
     }

@@ -5,6 +5,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "dcx_epi_lines.h"
+
 namespace dcx {
 
 typedef short s16x4p __attribute__((ext_vector_type(4)));
@@ -184,6 +186,25 @@ __device__ __forceinline__ void store_h2_8(unsigned short* base, long long row, 
   unsigned short* dst = base + row * (long long)C * 2 + (c >> 5) * 64 + ((c >> 3) & 3) * 16;
   *reinterpret_cast<s16x8p*>(dst) = hv;
   *reinterpret_cast<s16x8p*>(dst + 8) = lv;
+}
+// store_h2_8 by a lane pair: lanes 2 g and 2 g + 1 of a wave hold channels [c, c + 4) and
+// [c + 4, c + 8) of one row's unit (c a multiple of 8; both lanes active).  Each splits its own four
+// values; the even lane takes its partner's h and stores the unit's 16-byte h piece, the odd lane
+// its partner's l and the l piece (two packed dwords exchanged by DPP, quad_perm 1 0 3 2), so the
+// lanes of a row store 16 B each, contiguous (dcx_epi_lines.h).  c4: this lane's first channel.
+template <bool SAT = true>
+__device__ __forceinline__ void store_h2_pair(unsigned short* base, long long row, int C, int c4, const f32x4p& v,
+                                              float sc = 1.0f) {
+  unsigned short h[4], l[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) split2h<SAT>(v[e] * sc, h[e], l[e]);
+  const int h0 = h[0] | (h[1] << 16), h1 = h[2] | (h[3] << 16), l0 = l[0] | (l[1] << 16), l1 = l[2] | (l[3] << 16);
+  const bool odd = epi_h2_odd(c4);
+  const int g0 = __builtin_amdgcn_mov_dpp(odd ? h0 : l0, 0xB1, 0xF, 0xF, true);
+  const int g1 = __builtin_amdgcn_mov_dpp(odd ? h1 : l1, 0xB1, 0xF, 0xF, true);
+  typedef int i32x4p __attribute__((ext_vector_type(4)));
+  const i32x4p o = odd ? i32x4p{g0, g1, l0, l1} : i32x4p{h0, h1, g0, g1};
+  *reinterpret_cast<i32x4p*>(base + row * (long long)C * 2 + epi_h2_off(c4)) = o;
 }
 
 }  // namespace dcx
